@@ -7,12 +7,14 @@ Inputs (seeded, already resident in HBM): x_T ~ N(0,1), masked-image latent, ell
 c ~ N(0,1) [B,1,768], learned-uncond vector, scale 3.5, eta 0.  Weights: seeded random init of the exact
 REFace architecture (859.5 M-param UNet, 83.7 M-param VAE) -- no checkpoint is obtainable offline.
 
-  python bench.py --gpus N --steps K --warmup W [--config c1|c2|c3|c4]
+  python bench.py --gpus N --steps K --warmup W [--config c1|c2|c3|c4] [--dump-outputs DIR] [--full]
 N > 1 without a launcher: this process spawns `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child
 (before touching the GPU) and relays rank 0's line; under torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE.
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events per launch on the launch
-stream; `cpu_baseline` times the CPU oracle (oracle/) on a bounded sample of the same workload.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline line; --dump-outputs DIR
+also writes what the last timed step computed as DIR/<name>.npy.  Everything else is measured only under --full: `roofline` with HIP
+events per launch on the launch stream, the shader clock, the parity modes, the other configs, the conditioning stage, and
+`cpu_baseline`, which times the CPU oracle (oracle/) on a bounded sample of the same workload.
 """
 import argparse
 import json
@@ -48,8 +50,25 @@ CONFIGS = {
 }
 
 
+DUMP_BYTES = 64_000_000      # --dump-outputs: at most this many bytes of float32 in all
+
+
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(outdir, arrays):
+    """Write each tensor of `arrays` as <outdir>/<name>.npy in float32.  When they hold more than DUMP_BYTES in all, each is cut to the
+    same share of its flattened elements, picked by a fixed seed (the same indices from run to run)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    total = 4 * sum(t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if total > DUMP_BYTES:
+            k = a.size * DUMP_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def synthetic_inputs(B, h, seed, device):
@@ -467,8 +486,15 @@ def main():
     ap.add_argument("--profile-json", default=None, help="write the per-kernel-family table here")
     ap.add_argument("--overlap-decode", action="store_true", help="run the VAE decode of a batch on a second stream beside the next batch's DDIM loop")
     ap.add_argument("--no-other-configs", dest="other_configs", action="store_false",
-                    help="skip the short configs[3] (768x768) / configs[4] (fp8) lines the default c1 run appends under `other_configs`")
+                    help="skip the short configs[3] (768x768) / configs[4] (fp8) lines the --full c1 run appends under `other_configs`")
+    ap.add_argument("--full", action="store_true", help="after the headline line's steps, also measure and check everything else: shader clock, "
+                    "roofline and per-kernel tables, parity modes, the other configs, the conditioning stage, the CPU baseline, the per-rank weight checksum "
+                    "(each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (decoded images, DDIM latents) "
+                    "as DIR/<name>.npy in float32")
     args = ap.parse_args()
+    if args.profile_json and not args.full:
+        ap.error("--profile-json needs --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -496,7 +522,7 @@ def main():
     from reface_amd import ops
     from reface_amd.ddim import DDIMSampler
     dtype = {"bf16": torch.bfloat16, "fp16": torch.float16, "f32": torch.float32, "f32x3": "f32x3", "fp8": "fp8", "fp8w": "fp8w", "fp8c": "fp8c"}[dname]
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     unet, vae, ldm, cpu_sd = build_models(dtype, device, rank, world, want_cpu)
     sampler = DDIMSampler(ldm)
     x_T, z_inp, mask, c, uc = synthetic_inputs(B, h, 42 + rank, device)
@@ -505,11 +531,13 @@ def main():
     # --overlap-decode: the decode of batch i runs on a second HIP stream beside the DDIM loop of batch i + 1 (the CLI's serving form: the two
     # launch lists share nothing but the latents, handed over as a copy); the timed region still ends with a device-wide synchronize
     side = torch.cuda.Stream(device=device) if args.overlap_decode else None
+    last = {}
 
     def one_batch():
         samples, _ = sampler.sample(S=S, conditioning=c, batch_size=B, shape=[4, h, h], verbose=False,
                                     unconditional_guidance_scale=args.scale, unconditional_conditioning=uc, eta=0.0, x_T=x_T,
                                     test_model_kwargs={"inpaint_image": z_inp, "inpaint_mask": mask})
+        last["latents"] = samples
         if side is None:
             x = vae.decode(samples, inv_scale=1.0 / 0.18215)
             ops.to_image(x, img_out)()
@@ -546,8 +574,10 @@ def main():
         from reface_amd.multigpu import max_over_ranks
         elapsed = max_over_ranks(elapsed, "cpu" if args.share_gpu else device)
     assert torch.isfinite(out).all(), "non-finite output image"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"images": out, "latents": last["latents"]})
     wsums = None
-    if world > 1:
+    if world > 1 and args.full:
         # every rank must be running rank 0's weights (flat RCCL broadcast at start-up): one fp64 checksum per rank, gathered once
         import torch.distributed as dist
         cs = float(sum(p.detach().double().sum().item() for p in list(unet.parameters())[:64] + list(vae.parameters())[:64]))
@@ -583,7 +613,7 @@ def main():
         result["weights_checksum_per_rank"] = wsums
         result["weights_identical_on_all_ranks"] = all(w == wsums[0] for w in wsums)
     clk = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         try:
             clk = clock_under_load(sampler, dict(S=S, B=B, h=h, scale=args.scale, c=c, uc=uc, x_T=x_T, z_inp=z_inp, mask=mask), device)
         except Exception as e:          # a diagnostic: never in the way of the headline number
@@ -593,7 +623,7 @@ def main():
             result["clock_under_load_frac"] = clk["frac"]
             log(f"[bench] shader clock inside the DDIM loop: {clk['frac']:.3f} of the idle chip's (min {clk['in_loop_min'] / clk['fma_iters_per_10ns_tick_boost']:.3f})")
         one_batch()                     # (back to the whole-loop graph before the launch list is event-timed)
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         from reface_amd import profiler
         plan = list(sampler._plans.values())[0]
         log(f"[bench] UNet launches per DDIM step: {len(plan['step'])} (GroupNorm statistics fused into GEMM epilogues: {plan['eng'].gn_fused} of 61; "
@@ -670,7 +700,7 @@ def main():
             with open(args.profile_json, "w") as f:
                 json.dump({"families": fam, "vae_families": dfam, "step_launches": [row(l, ms) for l, ms in timed_l],
                            "vae_launches": [row(l, ms) for l, ms in dtimed]}, f, indent=1)
-    if rank == 0 and world == 1 and not args.no_parity and dname not in ("f32", "f32x3"):
+    if rank == 0 and world == 1 and args.full and not args.no_parity and dname not in ("f32", "f32x3"):
         try:
             # (a) the reduced-precision mode's image error against the exact-fp32 mode, full width, full S
             result[f"parity_{dname}_vs_f32"] = image_parity(unet, vae, ldm, h, S, args.scale, device)
@@ -700,7 +730,7 @@ def main():
             torch.cuda.empty_cache()
         except Exception as e:
             result["parity_mode"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and args.other_configs and cname == "c1" and args.batch is None and args.latent is None and args.dtype is None:
+    if rank == 0 and world == 1 and args.full and args.other_configs and cname == "c1" and args.batch is None and args.latent is None and args.dtype is None:
         # BASELINE configs[3] / configs[4] as short driver-visible lines (inside this run's wall clock): same models, same timed region
         # (barrier + synchronize around `steps` whole batches), their own roofline from the same event-timed launch list
         result["other_configs"] = {}
@@ -715,7 +745,7 @@ def main():
         unet.set_compute_dtype(dtype)
         vae._engines = {k: v for k, v in vae._engines.items() if (k[1], k[2]) == (B, h)}          # drop the other configs' decoders
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_conditioning:
+    if rank == 0 and world == 1 and args.full and not args.no_conditioning:
         try:
             result["conditioning"] = conditioning_line(vae, B, h, device)
             log(f"[bench] conditioning stage: {result['conditioning']['value']:.1f} images/s ({result['conditioning']['ms_per_batch']:.1f} ms per batch of {B})")

@@ -408,17 +408,20 @@ def test_resize_u8_linear_kernel_matches_host():
     assert np.array_equal(got[1].cpu().numpy(), resize_u8_linear(st[1], 224, 224))
 
 
-def test_bench_two_ranks_share_gpu():
+def test_bench_two_ranks_share_gpu(tmp_path):
     """The N > 1 path of bench.py end to end on one GPU: `--gpus 2 --share-gpu` spawns torch.distributed.run as a child (gloo, both ranks
     on cuda:0), rank 0 generates the weights and broadcasts them flat, the ranks shard the pairs, time = max over ranks.  Checks the
-    line the driver parses: n_gpus, a finite whole-job value, and that rank 1 ended up with rank 0's weights."""
+    line the driver parses: n_gpus, a finite whole-job value, that rank 1 ended up with rank 0's weights (a --full check), and the
+    outputs rank 0 dumps (--dump-outputs: its own images and latents, float32)."""
     import json
     import subprocess
     import sys
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "1", "--warmup", "0",
-                        "--no-cpu-baseline", "--no-roofline", "--no-parity", "--no-conditioning", "--ddim-steps", "10", "--batch", "2"],
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "1", "--warmup", "0", "--full",
+                        "--no-cpu-baseline", "--no-roofline", "--no-parity", "--no-conditioning", "--ddim-steps", "10", "--batch", "2",
+                        "--dump-outputs", str(dump)],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -426,6 +429,9 @@ def test_bench_two_ranks_share_gpu():
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 4 and d["scaling"] == "weak"
     assert d["value"] > 0 and d["value"] == d["value"] and d["ms_per_step"] > 0
     assert d["weights_identical_on_all_ranks"] is True and len(d["weights_checksum_per_rank"]) == 2, d.get("weights_checksum_per_rank")
+    img, lat = np.load(dump / "images.npy"), np.load(dump / "latents.npy")
+    assert img.shape == (2, 3, 512, 512) and lat.shape == (2, 4, 64, 64) and img.dtype == lat.dtype == np.float32
+    assert np.isfinite(lat).all() and img.min() >= 0.0 and img.max() <= 1.0
 
 
 def test_one_inference_caller(tmp_path):

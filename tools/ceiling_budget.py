@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The ceiling budget of one DDIM step: for every launch class of bench.py's `--profile-json` table
+"""The ceiling budget of one DDIM step: for every launch class of bench.py's `--full --profile-json` table
 
     floor = max(FLOP / R_best, compulsory bytes / BW [, exponentials / R_exp]) + T_launch
                                                                           R_best = 1.24 PFLOP/s  (the best ANY kernel has shown on this chip for this kind of GEMM:

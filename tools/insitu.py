@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-layer IN-SITU kernel times of one DDIM step: joins a rocprofv3 kernel trace of bench.py (graph replays) with the
-launch list written by `bench.py --profile-json` (isolated timings).  Usage: tools/insitu.py <kernel_trace.csv> <prof.json> [--by-shape]"""
+launch list written by `bench.py --full --profile-json` (isolated timings).  Usage: tools/insitu.py <kernel_trace.csv> <prof.json> [--by-shape]"""
 import collections
 import csv
 import json

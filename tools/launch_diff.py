@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-launch-class difference of two `bench.py --profile-json` tables (same config, two libraries / settings on one box):
+"""Per-launch-class difference of two `bench.py --full --profile-json` tables (same config, two libraries / settings on one box):
    python tools/launch_diff.py base.json other.json [min_us]"""
 import collections
 import json
