@@ -390,6 +390,23 @@ int rf_mul_mask(const float* x, const float* mask, int B, int C, int HW, float* 
 int rf_compose_outputs_u8(const float* result01, const float* target, const float* inpaint, const float* mask, const float* ref, int B, int H, int W,
                           int with_grid, void* out_u8, int64_t record_bytes, void* stream);
 int rf_resize_u8_linear(const void* x_u8, int B, int H, int W, int C, int64_t image_stride, int Ho, int Wo, void* out_u8, void* stream);
+/*
+ * BiSeNet face parser (pretrained/face_parsing/{model,resnet,face_parsing_demo}.py): the passes around its rf_conv_gemm convolutions.
+ * fp32 storage, channels-last.
+ *   rf_parse_prep    : uint8 HWC crops [B, H, W, 3] (H, W even, >= 4) -> fp32 [B, H/2, W/2, 8]: ToTensor (x / 255), BicubicDownSample(2)
+ *                      (8 cubic taps a = -0.5, reflect padding 3 | 3, vertical pass then horizontal pass, no rounding), clamp(0, 1),
+ *                      (x - ImageNet mean) / std; channels 3..7 zero (face_parsing_demo.py:116-185, 270-279)
+ *   rf_maxpool3x3s2  : MaxPool2d(3, 2, padding 1) of [B, H, W, C] -> [B, (H-1)/2+1, (W-1)/2+1, C], padding = -inf (resnet.py:58)
+ *   rf_add_relu      : out = relu(a + r), n elements (BasicBlock tail, resnet.py:41-47)
+ *   rf_scale_add_vec : out[b, p, c] = x[b, p, c] * s[b, c] + v[b, c] over [B, HW, C] (ARM32 + global context, model.py:99,121-122)
+ *   rf_parse_head    : logits [B, h, w, C] (pixel pitch ldl) -> uint8 [B, H, W]: lut256[argmax_c bilinear(align_corners=True)] with the
+ *                      first maximum winning; the upsampled logits are never stored (model.py:252, face_parsing_demo.py:293, 309-311)
+ */
+int rf_parse_prep(const void* x_u8, int B, int H, int W, float* out, void* stream);
+int rf_maxpool3x3s2(const float* x, int B, int H, int W, int C, float* out, void* stream);
+int rf_add_relu(const float* a, const float* r, float* out, int64_t n, void* stream);
+int rf_scale_add_vec(const float* x, const float* s, const float* v, float* out, int B, int HW, int C, void* stream);
+int rf_parse_head(const float* logits, int B, int h, int w, int C, int ldl, int H, int W, const void* lut256_u8, void* out_u8, void* stream);
 /* elementwise y = silu(x) on fp32 (emb path, openaimodel.py:219) */
 int rf_silu_f32(const float* x, float* y, int64_t n, void* stream);
 

@@ -951,6 +951,57 @@ def se_scale_add(r, s, shortcut, out, *, stride, name="se_scale_add"):
                                         stride, _p(out), B, Ho, Wo, Cc), (r, s, shortcut, out), name)
 
 
+def parse_prep(x_u8, out, name="parse_prep"):
+    """uint8 HWC crops [B, H, W, 3] -> fp32 [B, H/2, W/2, 8]: the face parser's ToTensor + BicubicDownSample(2) + clamp + normalise (rf_parse_prep)."""
+    lib = _lib.load()
+    _require_gpu(x_u8, out)
+    B, H, W_, Cc = x_u8.shape
+    assert x_u8.dtype == torch.uint8 and Cc == 3 and x_u8.is_contiguous()
+    assert out.dtype == torch.float32 and out.shape == (B, H // 2, W_ // 2, 8) and out.is_contiguous()
+    return Launch(lib.rf_parse_prep, (_p(x_u8), B, H, W_, _p(out)), (x_u8, out), name)
+
+
+def maxpool3x3s2(x, out, name="maxpool3x3s2"):
+    """MaxPool2d(3, 2, padding 1) of fp32 [B, H, W, C] -> [B, (H-1)//2+1, (W-1)//2+1, C] (rf_maxpool3x3s2)."""
+    lib = _lib.load()
+    _require_gpu(x, out)
+    B, H, W_, Cc = x.shape
+    assert x.dtype == out.dtype == torch.float32 and x.is_contiguous() and out.is_contiguous()
+    assert out.shape == (B, (H - 1) // 2 + 1, (W_ - 1) // 2 + 1, Cc)
+    return Launch(lib.rf_maxpool3x3s2, (_p(x), B, H, W_, Cc, _p(out)), (x, out), name)
+
+
+def add_relu(a, r, out, name="add_relu"):
+    """out = relu(a + r), fp32, same shapes (rf_add_relu)."""
+    lib = _lib.load()
+    _require_gpu(a, r, out)
+    assert a.dtype == r.dtype == out.dtype == torch.float32 and a.shape == r.shape == out.shape
+    assert a.is_contiguous() and r.is_contiguous() and out.is_contiguous()
+    return Launch(lib.rf_add_relu, (_p(a), _p(r), _p(out), a.numel()), (a, r, out), name)
+
+
+def scale_add_vec(x, s, v, out, name="scale_add_vec"):
+    """out[b, p, c] = x[b, p, c] * s[b, c] + v[b, c] on fp32 [B, ..., C] (rf_scale_add_vec)."""
+    lib = _lib.load()
+    _require_gpu(x, s, v, out)
+    B, Cc = x.shape[0], x.shape[-1]
+    HW = x.numel() // (B * Cc)
+    assert x.dtype == s.dtype == v.dtype == out.dtype == torch.float32 and x.shape == out.shape and x.is_contiguous() and out.is_contiguous()
+    assert s.shape == v.shape == (B, Cc) and s.is_contiguous() and v.is_contiguous()
+    return Launch(lib.rf_scale_add_vec, (_p(x), _p(s), _p(v), _p(out), B, HW, Cc), (x, s, v, out), name)
+
+
+def parse_head(logits, lut256, out, name="parse_head"):
+    """logits fp32 [B, h, w, C] (unit channel stride) -> uint8 [B, H, W] = lut256[argmax_c bilinear_align_corners(logits)] (rf_parse_head)."""
+    lib = _lib.load()
+    _require_gpu(logits, lut256, out)
+    B, h, w, Cc = logits.shape
+    Bo, H, W_ = out.shape
+    assert logits.dtype == torch.float32 and logits.stride(3) == 1 and logits.stride(1) == w * logits.stride(2) and logits.stride(0) == h * w * logits.stride(2)
+    assert Bo == B and out.dtype == torch.uint8 and out.is_contiguous() and lut256.dtype == torch.uint8 and lut256.numel() == 256 and lut256.is_contiguous()
+    return Launch(lib.rf_parse_head, (_p(logits), B, h, w, Cc, logits.stride(2), H, W_, _p(lut256), _p(out)), (logits, lut256, out), name)
+
+
 def adaptive_avgpool(x, out, *, crop=None, a=None, b=None, nhwc=False, name="adaptive_avgpool"):
     """x: NCHW fp32; crop = (y0, x0, h, w) window (default full).  out: NCHW fp32 [B,C,Ho,Wo] or (nhwc) [B,Ho,Wo,Cpad]."""
     lib = _lib.load()

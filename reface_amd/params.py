@@ -392,6 +392,50 @@ def arcface_param_specs():
     return s
 
 
+def bisenet_units():
+    """(prefix, cin, cout, stride) of the eight BasicBlocks of BiSeNet's ResNet-18 context path (resnet.py:50-64)."""
+    units = []
+    for li, (cin, cout, stride) in enumerate(((64, 64, 1), (64, 128, 2), (128, 256, 2), (256, 512, 2)), start=1):
+        units.append((f"cp.resnet.layer{li}.0", cin, cout, stride))
+        units.append((f"cp.resnet.layer{li}.1", cout, cout, 1))
+    return units
+
+
+def bisenet_param_specs(n_classes=19):
+    """State-dict keys of the face parser ``BiSeNet(n_classes=19)`` (pretrained/face_parsing/model.py:235-244, resnet.py:53-62), in module
+    order, auxiliary heads conv_out16 / conv_out32 included (the checkpoint carries them; the label map does not use them)."""
+    s = OrderedDict()
+
+    def cbr(p, cin, cout, k):               # ConvBNReLU: conv (no bias) + bn
+        s[f"{p}.conv.weight"] = (cout, cin, k, k)
+        _bn(s, f"{p}.bn", cout)
+
+    s["cp.resnet.conv1.weight"] = (64, 3, 7, 7)
+    _bn(s, "cp.resnet.bn1", 64)
+    for p, cin, cout, stride in bisenet_units():
+        s[f"{p}.conv1.weight"] = (cout, cin, 3, 3)
+        _bn(s, f"{p}.bn1", cout)
+        s[f"{p}.conv2.weight"] = (cout, cout, 3, 3)
+        _bn(s, f"{p}.bn2", cout)
+        if cin != cout or stride != 1:
+            s[f"{p}.downsample.0.weight"] = (cout, cin, 1, 1)
+            _bn(s, f"{p}.downsample.1", cout)
+    for arm, cin in (("cp.arm16", 256), ("cp.arm32", 512)):
+        cbr(f"{arm}.conv", cin, 128, 3)
+        s[f"{arm}.conv_atten.weight"] = (128, 128, 1, 1)
+        _bn(s, f"{arm}.bn_atten", 128)
+    cbr("cp.conv_head32", 128, 128, 3)
+    cbr("cp.conv_head16", 128, 128, 3)
+    cbr("cp.conv_avg", 512, 128, 1)
+    cbr("ffm.convblk", 256, 256, 1)
+    s["ffm.conv1.weight"] = (64, 256, 1, 1)
+    s["ffm.conv2.weight"] = (256, 64, 1, 1)
+    for head, cin, mid in (("conv_out", 256, 256), ("conv_out16", 128, 64), ("conv_out32", 128, 64)):
+        cbr(f"{head}.conv", cin, mid, 3)
+        s[f"{head}.conv_out.weight"] = (n_classes, mid, 1, 1)
+    return s
+
+
 def cond_head_specs():
     """Top-level LatentDiffusion conditioning heads (ddpm.py:698-733)."""
     s = OrderedDict()

@@ -4,8 +4,9 @@
 
 The reference script has two stages.  Stage 1 (:440-512) aligns and crops the raw ``--target_folder`` / ``--src_folder`` images
 (dlib / FFHQ alignment) and writes face-parsing label maps (BiSeNet, ``--faceParsing_ckpt``) into ``<Base_dir>/{target_cropped,
-mask_frames,source_cropped,source_mask}``; those models are outside the scope of this build, so this CLI expects
-that tree to exist (the reference's stage 1, or any tool writing ``<i>.png`` crops + label maps, produces it).  Stage 2 -- the
+mask_frames,source_cropped,source_mask}``.  The alignment is outside the scope of this build, so this CLI expects
+the crops to exist (the reference's stage 1, or any tool writing ``<i>.png`` crops + label maps, produces them); ``--parse_masks`` writes
+missing label maps from the crops with the GPU face parser (reface_amd/parsing.py).  Stage 2 -- the
 sampling loop -- is the same batch body as the test bench (reface_amd/pipeline.py) with ONE source face repeated over the batch
 (:649-653); outputs as the reference writes them: ``<outdir>/results/<s>/<id>.png``, ``<outdir>/grid/<s>/grid-<id>.png``,
 ``<outdir>/<s>/<id>_{mask,GT,inpaint,ref}.png`` and the decoded ``pred_x0`` intermediates in ``<outdir>/model_outputs``.
@@ -69,6 +70,8 @@ def build_parser():
     p.add_argument("--dump_tensors", type=str, default=None, help="directory for per-batch .npz dumps of the tensors fed to / produced by the engines (tests)")
     p.add_argument("--clip_vision_config", type=str, default=None, help="JSON dict overriding the CLIP ViT dims (tests)")
     p.add_argument("--num_workers", type=int, default=4)
+    p.add_argument("--parse_masks", action="store_true", help="write missing face-parsing label maps from the existing crops with the GPU "
+                   "face parser (--faceParsing_ckpt, 'none' = seeded weights; --seg12) before sampling")
     return p
 
 
@@ -80,6 +83,13 @@ def main(argv=None):
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     base = opt.Base_dir
     tc, tm, sc, sm = (os.path.join(base, d) for d in ("target_cropped", "mask_frames", "source_cropped", "source_mask"))
+    if opt.parse_masks:             # stage 1's parsing half on the GPU: label maps of the crops whose map folder is missing or empty
+        from reface_amd.parsing import parse_label_maps
+        jobs = []
+        for crops, maps in ((tc, tm), (sc, sm)):
+            if os.path.isdir(crops) and os.listdir(crops) and not (os.path.isdir(maps) and os.listdir(maps)):
+                jobs += [(os.path.join(crops, f), os.path.join(maps, f)) for f in sorted(os.listdir(crops))]
+        print(f"inference_swap_selected: {parse_label_maps(jobs, opt.faceParsing_ckpt, seg12=opt.seg12)} label maps written by the face parser")
     missing = [d for d in (tc, tm, sc, sm) if not os.path.isdir(d) or not os.listdir(d)]
     if missing:
         raise SystemExit("inference_swap_selected: stage 1 of the reference (face alignment + BiSeNet parsing of --target_folder / "

@@ -6,7 +6,8 @@ The reference script has three stages.  Stage 1 (:430-500) decodes ``--target_vi
 ``--src_image`` (dlib / FFHQ alignment, keeping the inverse transforms) and writes face-parsing label maps (BiSeNet); stage 3
 (:690-760) warps every swapped crop back into its frame and encodes the mp4 with the original audio (moviepy).  Both are host-side
 I/O around models that are outside this build, so this CLI takes stage 1's on-disk product, in the reference's
-own layout, and leaves stage 3 to the reference:
+own layout, and leaves stage 3 to the reference (``--parse_masks`` writes the label maps below from the crops with the GPU face parser,
+reface_amd/parsing.py, when they are missing):
 
   <Base_dir>/<video>cropped_face/<i>.png      aligned 1024^2 crops, one per frame           (:416, written at :489)
   <Base_dir>/<video>mask_frames/<i>.png       their face-parsing label maps                 (:417, :497)
@@ -77,6 +78,8 @@ def build_parser():
     p.add_argument("--dump_tensors", type=str, default=None, help="directory for per-batch .npz dumps of the tensors fed to / produced by the engines (tests)")
     p.add_argument("--clip_vision_config", type=str, default=None, help="JSON dict overriding the CLIP ViT dims (tests)")
     p.add_argument("--num_workers", type=int, default=4)
+    p.add_argument("--parse_masks", action="store_true", help="write missing face-parsing label maps from the existing crops with the GPU "
+                   "face parser (--faceParsing_ckpt, 'none' = seeded weights; --seg12) before sampling")
     return p
 
 
@@ -96,6 +99,14 @@ def main(argv=None):
     np.random.seed(opt.seed)
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     pp = prepared_paths(opt)
+    if opt.parse_masks:             # stage 1's parsing half on the GPU: label maps of the frame crops / source crop that lack them
+        from reface_amd.parsing import parse_label_maps
+        jobs = []
+        if os.path.isdir(pp["frames"]) and os.listdir(pp["frames"]) and not (os.path.isdir(pp["masks"]) and os.listdir(pp["masks"])):
+            jobs += [(os.path.join(pp["frames"], f), os.path.join(pp["masks"], f)) for f in sorted(os.listdir(pp["frames"]))]
+        if os.path.isfile(pp["src"]) and not os.path.isfile(pp["src_mask"]):
+            jobs.append((pp["src"], pp["src_mask"]))
+        print(f"inference_swap_video: {parse_label_maps(jobs, opt.faceParsing_ckpt, seg12=opt.seg12)} label maps written by the face parser")
     missing = [pp[k] for k in ("frames", "masks") if not os.path.isdir(pp[k]) or not os.listdir(pp[k])]
     missing += [pp[k] for k in ("src", "src_mask") if not os.path.isfile(pp[k])]
     if missing:

@@ -8,7 +8,7 @@ as small ``.npz`` fixtures under tests/golden/.  Only DATA is stored (tensors + 
 needed to regenerate the weights); no reference source is copied.
 
 Usage:  python tools/gen_golden.py [group ...]     (groups: schedule unet_ops unet_small unet_full
-                                                    ddim vae arcface clip e2e)
+                                                    ddim vae arcface clip e2e bisenet)
 """
 import os
 import sys
@@ -506,8 +506,83 @@ def gen_e2e():
     save("e2e_png", grid=g0, mask=written["a_mask.png"])
 
 
+def seeded_u8(shape, seed):
+    """Deterministic uint8 image tensor (the parser fixtures' inputs; tests/test_parsing_gpu.py regenerates them the same way)."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(int(seed))
+    return torch.randint(0, 256, tuple(shape), generator=g, dtype=torch.uint8)
+
+
+def _import_face_parsing():
+    """The reference's face parser modules, imported without network, GPU or OpenCV:
+    * model.py moves seg_mean / seg_std to the GPU at import time: Tensor.cuda is the identity during that import only;
+    * face_parsing_demo.py imports cv2 (absent here): a stub module;
+    * Resnet18.__init__ calls model_zoo.load_url(resnet18_url), which would DOWNLOAD the ImageNet weights: load_url and
+      load_state_dict_from_url are replaced by stubs returning an empty dict (no I/O) -- the seeded weights are loaded afterwards.
+    The repository ships its own `pretrained` package (the drop-in demo module): `pretrained` is pinned to the reference tree."""
+    import types
+    import torch.hub
+    import torch.utils.model_zoo
+    no_io = lambda *a, **k: {}                  # noqa: E731
+    torch.utils.model_zoo.load_url = no_io
+    torch.hub.load_state_dict_from_url = no_io
+    if "cv2" not in sys.modules:
+        sys.modules["cv2"] = types.ModuleType("cv2")
+    pre = types.ModuleType("pretrained")
+    pre.__path__ = ["/root/reference/pretrained"]
+    sys.modules["pretrained"] = pre
+    cuda = torch.Tensor.cuda
+    torch.Tensor.cuda = lambda self, *a, **k: self
+    try:
+        import pretrained.face_parsing.model as fpm
+        import pretrained.face_parsing.face_parsing_demo as fpd
+    finally:
+        torch.Tensor.cuda = cuda
+    assert fpm.seg_mean.device.type == "cpu"
+    return fpm, fpd
+
+
+def gen_bisenet():
+    """BiSeNet face parser (pretrained/face_parsing/): key layout, seg12 LUT, prep output and the 64^2 logits + 512^2 label maps of a 1024^2
+    batch, all from the reference's own modules on CPU with seeded weights."""
+    import json
+    import torch.nn.functional as F
+    fpm, fpd = _import_face_parsing()
+    import torch.utils.model_zoo
+    assert torch.utils.model_zoo.load_url("x") == {}            # never construct the net without the no-download stub
+    net = fpm.BiSeNet(n_classes=19).eval()
+    keys = [[k, list(v.shape)] for k, v in net.state_dict().items()]
+    sd = P.seeded_state_dict(P.bisenet_param_specs(), 91)
+    load_strict(net, sd)
+    path = os.path.join(OUT, "bisenet_keys.json")
+    json.dump(keys, open(path, "w"), separators=(",", ":"))
+    print(f"  wrote {path}  ({len(keys)} keys)")
+    conv = getattr(fpd, "__ffhq_masks_to_faceParser_mask_detailed")        # module-level double-underscore name: no mangling
+    lut = conv(np.arange(19, dtype=np.uint8))
+    down = fpd.BicubicDownSample(factor=2, cuda=False)
+
+    def prep(u8):                                # FaceParser.preprocess_img on a batch (>= 512 px branch): ToTensor -> downsample -> clamp -> normalise
+        x = u8.permute(0, 3, 1, 2).float().div(255)
+        return (down(x).clamp(0, 1) - fpm.seg_mean) / fpm.seg_std
+
+    small = seeded_u8((1, 96, 128, 3), 92)
+    prep_small = prep(small)
+    big = seeded_u8((2, 1024, 1024, 3), 93)
+    xb = prep(big)
+    got = {}
+    h = net.conv_out.register_forward_hook(lambda m, i, o: got.__setitem__("logits", o))
+    out = net(xb)[0]
+    h.remove()
+    labels = torch.argmax(out, dim=1).numpy().astype(np.uint8)
+    assert np.array_equal(F.interpolate(got["logits"], (512, 512), mode="bilinear", align_corners=True).argmax(1).numpy(), labels)
+    seg12 = np.stack([conv(l) for l in labels])
+    save("bisenet", lut_seg12=lut, prep_small=prep_small, logits=got["logits"], labels=labels, labels_seg12=seg12,
+         seed=91, small_seed=92, big_seed=93)
+
+
 GROUPS = dict(ddim_full=gen_ddim_full, unet_keys=gen_unet_keys, plms=gen_plms, schedule=gen_schedule, unet_ops=gen_unet_ops, unet_small=gen_unet_small, unet_full=gen_unet_full,
-              ddim=gen_ddim, vae=gen_vae, arcface=gen_arcface, clip=gen_clip, e2e=gen_e2e)
+              ddim=gen_ddim, vae=gen_vae, arcface=gen_arcface, clip=gen_clip, e2e=gen_e2e,
+              bisenet=gen_bisenet)
 
 if __name__ == "__main__":
     sel = sys.argv[1:] or [g for g in GROUPS if g != "ddim_full"]          # (ddim_full: 20 minutes; ask for it by name)
