@@ -734,10 +734,6 @@ __global__ __launch_bounds__(256, (D < 48 ? 2 : 1)) void attention_dma_kernel(co
     const int bh = bid / p.nqb, qblk = bid - bh * p.nqb;
     const int b = bh / p.heads, h = bh % p.heads;
     const int q0 = qblk * (4 * 32 * QB) + wave * (32 * QB);
-#ifdef RF_ATTN_STAMP          // (experiment builds: cycle stamps of the kernel's phases, written over the first output row of every wave -- tools/archive/attn_stamp.py)
-    long long stamp_[5];
-    stamp_[0] = __builtin_readcyclecounter();
-#endif
     const T* Q = (const T*)p.q + b * p.sq + h * D;
     const T* K = (const T*)p.k + b * p.sk + h * D;
     const T* V = (const T*)p.v + b * p.sv + h * D;
@@ -902,9 +898,6 @@ __global__ __launch_bounds__(256, (D < 48 ? 2 : 1)) void attention_dma_kernel(co
             _Pragma("unroll") for (int i = 0; i < DVB; ++i)                                                     \
                 _Pragma("unroll") for (int qb = 0; qb < QB; ++qb) AttnMma<T>::mma(o[qb][i], vf[g][i], pf[qb][g]);                    \
     }
-#ifdef RF_ATTN_STAMP
-    stamp_[1] = __builtin_readcyclecounter();
-#endif
     RF_LOAD_KF(smem, 0)
     RF_WAIT_KF()
     RF_QK(S[0])
@@ -991,13 +984,7 @@ __global__ __launch_bounds__(256, (D < 48 ? 2 : 1)) void attention_dma_kernel(co
             unit(std::integral_constant<int, 3>{});
         }
         sc = sn;
-#ifdef RF_ATTN_STAMP
-        if (t == 0) stamp_[2] = __builtin_readcyclecounter();
-#endif
     }
-#ifdef RF_ATTN_STAMP
-    stamp_[3] = __builtin_readcyclecounter();
-#endif
     RF_WAIT_VF()
     RF_PV()
 #undef RF_WAIT_VF
@@ -1045,16 +1032,6 @@ __global__ __launch_bounds__(256, (D < 48 ? 2 : 1)) void attention_dma_kernel(co
                 }
         }
     }
-#ifdef RF_ATTN_STAMP
-    stamp_[4] = __builtin_readcyclecounter();
-    if (lane == 0 && q0 < p.Nq) {
-        int* const dst = (int*)(O + (long long)q0 * p.ldo);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dst[i] = (int)(stamp_[i + 1] - stamp_[i]);
-        dst[4] = (int)(stamp_[0] & 0x7fffffff);
-    }
-#endif
 }
 
 template <typename T, int D, int KT>
@@ -1064,9 +1041,7 @@ static int launch_attn_dma(const AttnParams& p, int B, hipStream_t st) {
     RF_RAISE_LDS(k, smem, "rf_attention");
     AttnParams pp = p;
     pp.nqb = (p.Nq + 255) / 256;
-    static const int pad = tune_env("RF_ATTN_SMEM_PAD", 0);      // experiment: one block per CU
-    if (pad) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem + pad);
-    hipLaunchKernelGGL(k, dim3(pp.nqb * B * p.heads), dim3(256), smem + pad, st, pp);
+    hipLaunchKernelGGL(k, dim3(pp.nqb * B * p.heads), dim3(256), smem, st, pp);
     RF_LAUNCH_CHECK("rf_attention");
     return 0;
 }
@@ -1093,20 +1068,14 @@ static int launch_attn(const AttnParams& p, int B, hipStream_t st) {
     // QB = 2 (two query blocks per wave, every K / V^T fragment feeds two MFMAs) pays for the small head dim when the
     // grid still fills the chip: d=40, N=4096: 687 us vs 739 us; it loses at d=80 (N=1024: 99 us vs 85 us).
     if constexpr (sizeof(T) == 2 && D <= 40) {
-        static const int kt = tune_env("RF_ATTN_KT", 128);
         if ((long long)((p.Nq + 255) / 256) * B * p.heads >= 512) {
-            // long sequences of whole 64-key tiles: the in-wave software-pipelined kernel (RF_ATTN_PIPE=0: the generic one)
-            static const int pipe = tune_env("RF_ATTN_PIPE", 1);
+            // long sequences of whole 64-key tiles: the in-wave software-pipelined kernel
             if constexpr (D == 40) {
-                static const int kt128 = tune_env("RF_ATTN_KT128", 1);
-                if (pipe && kt128 && p.Nk % 128 == 0 && p.Nk >= 1024) return launch_attn_dma<T, D, 128>(p, B, st);
-                if (pipe && p.Nk % 64 == 0 && p.Nk >= 1024) return launch_attn_dma<T, D, 64>(p, B, st);
+                if (p.Nk % 128 == 0 && p.Nk >= 1024) return launch_attn_dma<T, D, 128>(p, B, st);
+                if (p.Nk % 64 == 0 && p.Nk >= 1024) return launch_attn_dma<T, D, 64>(p, B, st);
             }
-            // 8-wave blocks (both waves of a SIMD on one staged tile) measured 608 vs 586 us at N = 4096: opt-in only (RF_ATTN_NW=8)
-            static const int nw = tune_env("RF_ATTN_NW", 4);
-            if (kt == 128 && p.Nk >= 1024 && nw == 8 && (long long)((p.Nq + 511) / 512) * B * p.heads >= 512)
-                return launch_attn_qb<T, D, 2, 128, 8>(p, B, st);
-            if (kt == 128 && p.Nk >= 1024) return launch_attn_qb<T, D, 2, 128>(p, B, st);
+            // (4-wave blocks: 8-wave blocks -- both waves of a SIMD on one staged tile -- measured 608 vs 586 us at N = 4096)
+            if (p.Nk >= 1024) return launch_attn_qb<T, D, 2, 128>(p, B, st);
             return launch_attn_qb<T, D, 2>(p, B, st);
         }
     }
@@ -1114,9 +1083,8 @@ static int launch_attn(const AttnParams& p, int B, hipStream_t st) {
     // 73 us against 85 at N = 1024 (tools/archive/run_r04x.sh: 64-key stages with 8 waves 85, 128-key stages with 4 waves 105, two query blocks per wave 81-99).
     // d = 160 keeps the 4-wave / 64-key form (N = 256: four stages of 64 keys already cover the sequence).
     if constexpr (sizeof(T) == 2 && D == 80) {
-        // whole 128-key tiles: the in-wave software-pipelined kernel, one wave per SIMD (RF_ATTN_PIPE80=0 in experiment builds: the generic one)
-        static const int pipe80 = tune_env("RF_ATTN_PIPE80", 1);
-        if (pipe80 && p.Nk % 128 == 0 && p.Nk >= 384) return launch_attn_dma<T, D, 128>(p, B, st);
+        // whole 128-key tiles: the in-wave software-pipelined kernel, one wave per SIMD
+        if (p.Nk % 128 == 0 && p.Nk >= 384) return launch_attn_dma<T, D, 128>(p, B, st);
         if (p.Nk >= 512 && (long long)((p.Nq + 255) / 256) * B * p.heads >= 256) return launch_attn_qb<T, D, 1, 128, 8>(p, B, st);
     }
     return launch_attn_qb<T, D, 1>(p, B, st);

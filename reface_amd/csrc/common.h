@@ -24,19 +24,7 @@ namespace rf {
 
 void set_error(const char* fmt, ...);
 
-// Tuning / experiment switches (tile overrides, epilogue forms, attention variants, the RF_GEMM_DBG timing decompositions) exist only in
-// builds made with -DRF_EXPERIMENT (tools/build_variant.sh, loaded through REFACE_HIP_LIB for same-box A/B runs).  The release library
-// reads NO environment variable: a stray variable in a user's shell cannot change -- or, for the timing decompositions, corrupt -- results.
-#ifdef RF_EXPERIMENT
-static inline int tune_env(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-#define RF_DBG(p, bits) ((p).dbg & (bits))
-#else
-static inline int tune_env(const char*, int dflt) { return dflt; }
-#define RF_DBG(p, bits) 0
-#endif
+// The library reads NO environment variable: a stray variable in a user's shell cannot change its results.
 
 #define RF_CHECK(cond, ...)                                     \
     do {                                                        \

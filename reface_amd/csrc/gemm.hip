@@ -20,32 +20,15 @@
 
 #include "common.h"
 
-// How the LDS-DMA pieces of tile kt+2 are issued behind the barrier that frees their stage (same-box A/B on the whole benchmark, r03):
-//   0: one burst (both waves of every SIMD stall on ~9 x 60-180 issue cycles at the same time)        935.9 / 933.6 ms per batch
-//   1: between the MFMA columns of k-step 3 (the issue slots hide under the matrix pipe)              921.4 / 920.0      <- default
-//   2: as 1 with the barrier ahead of all of k-step 3's columns                                      920.4 / 920.5 (vs 921.5 / 921.6 for 1 on that box)
-//   3: in thirds over k-step 3 and k-steps 0 / 1 of the next tile                                    965.3 / 964.1 (vs 939.9 / 937.0 for 1 on that box)
-#ifndef RF_SPREAD_DMA
-#define RF_SPREAD_DMA 1
-#endif
-
-// Experiment (RF_STORE_SC1 = 1): the direct epilogue's output stores as write-through `sc1` stores -- the bytes leave the XCD's L2 while the
-// kernel runs instead of in the write-back burst at the kernel boundary (every dirty line must reach the memory side before the next kernel
-// starts: the 8 L2s are not coherent), at the price of dropping the line from this XCD's L2.
-#ifndef RF_STORE_SC1
-#define RF_STORE_SC1 0
-#endif
+// The LDS-DMA pieces of tile kt+2 are issued between the MFMA columns of k-step 3, behind the barrier that frees their stage: the issue
+// slots hide under the matrix pipe.  Issue orders measured against it (same-box A/B on the whole benchmark, r03):
+//   one burst (both waves of every SIMD stall on ~9 x 60-180 issue cycles at the same time)        935.9 / 933.6 ms per batch
+//   between the MFMA columns of k-step 3 (kept)                                                     921.4 / 920.0
+//   as kept with the barrier ahead of all of k-step 3's columns                                    920.4 / 920.5 (vs 921.5 / 921.6 for the kept order on that box)
+//   in thirds over k-step 3 and k-steps 0 / 1 of the next tile                                      965.3 / 964.1 (vs 939.9 / 937.0 for the kept order on that box)
 
 namespace rf {
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void st16_out(void* ptr, const u32x4_t& w) {
-#if RF_STORE_SC1
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(ptr), "v"(w) : "memory");
-#else
-    *(u32x4_t*)ptr = w;
-#endif
-}
 
 struct GemmParams {
     int M, N, K;
@@ -81,7 +64,6 @@ struct GemmParams {
     int gn_cpg[2], gn_coff[2], gn_slot[2], gn_nch[2];
     int* plan;       // host only: rf_conv_gemm_plan / rf_conv_gemm_plan2 (no launch): {stat rows, stat cols, splitk, BM, BN, 32 TN, epilogue form, frag slabs}
     int epi2_ok;     // host only: operand alignment / feature set allow the direct (register -> global) epilogue
-    int dbg;         // RF_GEMM_DBG (timing experiments only): bit 0 = skip the epilogue, bit 1 = skip the main loop
     const float* wscale;   // W8 kernels: per-output-channel power-of-two scale of the fp8 (e4m3fn) weights
     void* oscale;          // A8 kernels with GEGLU: `out` receives e4m3fn bytes (pitch ldo BYTES) and oscale one E8M0 code per (row, 32 output columns)
     int os_ld;
@@ -118,13 +100,7 @@ __device__ __forceinline__ u32x4_t fp8x8_to_bf16x8(const u32x2_t& r, float scale
 template <typename T> struct MmaFrag;
 template <> struct MmaFrag<bf16_t> {
     __device__ static __forceinline__ void mma(f32x16_t& acc, const u32x4_t& a, const u32x4_t& b) {
-#if RF_PIN_MFMA
-        // experiment: MFMAs as volatile asm statements -- their order against each other and against the loop's waits / barrier is then the
-        // source order (what fixed the fp8 x fp8 loop, where the builtin form was sunk below every fragment load)
-        asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
-#else
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
-#endif
     }
 };
 template <> struct MmaFrag<f16_t> {
@@ -183,7 +159,7 @@ template <typename X> struct is16 { static constexpr bool value = std::is_same<X
 // (m = l & 31, h = l >> 5) ends up with accumulator register r = output column 16*h + r of its row: 16 CONTIGUOUS columns per
 // 32x32 block.  Bias / timestep vector / residual / GEGLU then happen in registers and every lane writes its row segments with 16-byte
 // stores -- no staging pass of the tile through LDS (only the BN column constants are parked there, one barrier), and the waves
-// retire independently.  EPI = 2: the whole tile staged ONCE as bf16 by all waves (opt-in, measured neutral).
+// retire independently.
 // W8 = true: the weights are fp8 (e4m3fn) with one power-of-two scale per output channel.  A W tile in LDS keeps the 128-byte row
 // geometry and therefore holds 128 K elements = the W operand of TWO consecutive A tiles: the W pieces are issued every other
 // tile (half the weight bytes through L2 / LDS), and a W fragment is an 8-byte LDS read turned into 8 bf16 by 4 conversions
@@ -198,9 +174,8 @@ template <typename X> struct is16 { static constexpr bool value = std::is_same<X
 template <typename T, typename TO, int WM, int WN, int TM, int TN, bool CONV, bool GLDS, int NST, int EPI = 0, bool W8 = false, int LNF = 0, bool HX = false>
 __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams p) {
     static_assert(LNF == 0 || (EPI == 1 && !CONV && !W8 && sizeof(T) == 2 && sizeof(TO) == 2), "LayerNorm folding: bf16 linear layers on the direct epilogue");
-    static_assert(!HX || (CONV && GLDS && NST == 2 && sizeof(T) == 2 && !W8 && EPI != 2), "row-extended A tiles: bf16 3x3 convolutions on the two-stage direct-to-LDS loop");
-    static_assert(EPI == 0 || GLDS, "the direct / packed epilogues are built on the direct-to-LDS main loop");
-    static_assert(EPI != 2 || std::is_same<TO, bf16_t>::value, "the packed staged epilogue writes bf16");
+    static_assert(!HX || (CONV && GLDS && NST == 2 && sizeof(T) == 2 && !W8), "row-extended A tiles: bf16 3x3 convolutions on the two-stage direct-to-LDS loop");
+    static_assert(EPI == 0 || GLDS, "the direct epilogue is built on the direct-to-LDS main loop");
     static_assert(!W8 || (GLDS && std::is_same<T, bf16_t>::value), "fp8 weights: bf16 activations on the direct-to-LDS main loop");
     // A8: fp8 (e4m3fn) activations with one E8M0 scale per 32 channels x fp8 weights with one power-of-two scale per output channel on
     // v_mfma_scale_f32_32x32x64_f8f6f4: a K tile (128-byte rows) holds 128 K elements, two k-steps of 64
@@ -259,7 +234,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
 
     // EPI 1: the per-column constants of this tile (bias + the tile's timestep / context vector) are fetched NOW, one column per
     // thread, and parked in LDS after the main loop: fetched in the epilogue they cost one exposed L2 / HBM round trip per
-    // 32-column block (5 per tile: 25 of the 60 us of the 65536x960x320 qkv GEMM, RF_GEMM_DBG=8 experiment r02g)
+    // 32-column block (5 per tile: 25 of the 60 us of the 65536x960x320 qkv GEMM, no-store timing experiment r02g)
     float colc = 0.f;
     if constexpr (EPI == 1) {
         if (tid < BN && n0 + tid < p.N && p.splitk == 1) {
@@ -271,26 +246,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
     if constexpr (LNF == 2) {
         if (tid < BN && n0 + tid < p.N) colu = p.ln_u[n0 + tid];
     }
-#if RF_RES_TOUCH
-    // experiment: pull the residual rows of this tile into L2 now (one dword per 128-byte line, data discarded), so that the epilogue's residual
-    // segments do not wait out HBM latency three times per wave tile
-    uint32_t touch_[4] = {0u, 0u, 0u, 0u};
-    if constexpr (EPI == 1) {
-        if (p.residual && p.splitk == 1) {
-            constexpr int EPL = 128 / (int)sizeof(TO), LPR = (BN + EPL - 1) / EPL;
-            const TO* const rbase = (const TO*)p.residual + zb * p.sR;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int i = tid + k * NT;
-                const int row = m0 + i / LPR, c = n0 + (i % LPR) * EPL;
-                if (i < BM * LPR && row < p.M && c < p.N) {
-                    const TO* ptr = rbase + (long long)row * p.ldr + c;
-                    asm volatile("global_load_dword %0, %1, off" : "=v"(touch_[k]) : "v"(ptr) : "memory");
-                }
-            }
-        }
-    }
-#endif
     const int r0 = tid >> 3;
     // GLDS: the LDS image of a direct-to-LDS load is lane-linear, so the XOR swizzle moves to the SOURCE: the lane that
     // lands on 16-byte position p of row r fetches k-slot p ^ ((r >> 1) & 7)  (r0 + 32*i keeps (r >> 1) & 7 for every i)
@@ -389,7 +344,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    int nk = (RF_DBG(p, 2)) ? 0 : (p.K + BK - 1) / BK;
+    int nk = (p.K + BK - 1) / BK;
     int kb0_tiles = 0;       // first K tile of this block (split-K)
     if (p.splitk > 1) {          // this block's K-tile range [kb0, kb0 + nk)
         int per = (nk + p.splitk - 1) / p.splitk;
@@ -586,9 +541,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
             for (int q = 0; q < NP; ++q) {
                 if (q >= q0 && q < q1) {
                     if (q < AV) {
-                        // (RF_GEMM_DBG bit 8, timing only: the A pieces of two K tiles out of three are not issued -- the fill a row-extended A
-                        //  tile shared by the three horizontal taps of a 3x3 window would need; stale operands, wrong results)
-                        if (!(RF_DBG(p, 256) && CONV && p.KW == 3 && p.stride == 1 && !p.ups && (it % 3) != 0) && !(HX && hx_dx != 0))
+                        if (!(HX && hx_dx != 0))
                             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (__attribute__((address_space(3))) void*)(a + q * (RPP * 128)), 16, offs[q], soA, 0, 0);
                     } else
                         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (__attribute__((address_space(3))) void*)(b + (q - AV) * (RPP * 128)), 16, offs[q], soB, 0, 0);
@@ -671,7 +624,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                 for (int j = JS8; j < TN; ++j) {
                     mma_col(cur, j);
                     ld_b(j, nB, nkk);
-                    if (kk == 1) {          // the pieces of tile kt+2 go out between the MFMA columns behind the barrier (RF_SPREAD_DMA 1)
+                    if (kk == 1) {          // the pieces of tile kt+2 go out between the MFMA columns behind the barrier
                         constexpr int COLS = TN - JS8, PPC = (NP + COLS - 1) / COLS;
                         if (more) issue_pieces(stage, (j - JS8) * PPC, (j - JS8 + 1) * PPC < NP ? (j - JS8 + 1) * PPC : NP);
                     }
@@ -694,11 +647,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
 #pragma unroll
                 for (int j = 0; j < TN; ++j) ld_b(j, curB, 0);
             }
-#if RF_RES_TOUCH
-            // (the touch loads are older than every piece: the prologue's wait covered them; their registers are free from here on)
-            if (nk == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            asm volatile("" ::"v"(touch_[0]), "v"(touch_[1]), "v"(touch_[2]), "v"(touch_[3]));
-#endif
             for (int kt = 0; kt < nk; ++kt) {
                 const int stage = kt & 1;
                 const bool more = kt + 2 < nk;
@@ -719,7 +667,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
         // Small wave tiles keep two full fragment sets; the 2x5 wave tile has no registers for that and rotates its B fragments
         // in place: column j of the next k-step is fetched right after column j's MFMAs have been issued.
         constexpr bool ROT = TM * TN > 8;
-        constexpr int JS_ = ROT ? 2 : 0;      // B columns whose MFMAs go ahead of the first next-fragment reads
+        constexpr int JS = ROT ? 2 : 0;       // B columns whose MFMAs go ahead of the first next-fragment reads
         u32x4_t fa[2][TM], fb[W8 ? 1 : 2][W8 ? 1 : TN];
         u32x2_t fbr[W8 ? 2 : 1][W8 ? TN : 1];          // W8: raw 8-byte fp8 fragments
         float ws[W8 ? TN : 1];                         // W8: scale of this lane's W row in each 32-row block
@@ -784,20 +732,14 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
             else return fb[set][j];
         };
         // one k-step: its MFMAs, the fetch of the next step's fragments (k-step 3 fetches from the other stage, after the
-        // barrier; on the last tile that fetch reads stale bytes that are never used) and a third of the next tile's pieces
-        const bool late = RF_SPREAD_DMA == 4 && NT == 512 && wave_u >= 4;
-        auto phase = [&](auto KK, int stage, bool more, bool deep, bool cont = false) {
+        // barrier; on the last tile that fetch reads stale bytes that are never used) and, at k-step 3, the pieces of tile kt+2
+        auto phase = [&](auto KK, int stage, bool more, bool deep) {
             constexpr int kk = decltype(KK)::value;
             constexpr int cur = kk & 1, nx = cur ^ 1;
             constexpr int fbc = ROT ? 0 : cur, fbn = ROT ? 0 : nx;
             constexpr int nkk = (kk + 1) & 3;
             const char* const nA = (kk < 3 ? curA : othA) + fk[nkk];
             const char* const nB = (kk < 3 ? curB : othB) + (fkb[nkk] ^ (kk < 3 ? curPar : othPar));
-#if RF_SPREAD_DMA == 2
-            constexpr int JS = (kk == 3 && ROT) ? 0 : JS_;          // k-step 3: barrier first, every MFMA column behind it takes its share of the pieces
-#else
-            constexpr int JS = JS_;
-#endif
 #pragma unroll
             for (int j = 0; j < JS; ++j) {
                 const u32x4_t bj = bfrag(fbc, j);
@@ -812,7 +754,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                 // that holds for all waves: this stage may be overwritten (tile kt+2) and the other stage may be read
                 // (NST > 2: tiles kt+2 .. kt+NST-1 stay in flight behind the one that must have landed -- `deep` says all of them exist)
                 if (NST > 2 && deep) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((NST - 2) * NP) : "memory");
-                else if (RF_DBG(p, 64)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // timing decomposition: the pieces are never waited for
                 else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
             }
@@ -823,10 +764,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
             }
 #pragma unroll
             for (int j = 0; j < (ROT ? JS : TN); ++j) load_b(fbn, j, nB + j * 4096);
-#if !RF_SPREAD_DMA
-            if (kk == 3 && more && !RF_DBG(p, 32)) issue_pieces(stage, 0, NP);      // 'more' here: tile kt+2 exists  (RF_GEMM_DBG bit 5: no DMA in
-                                                                                    // the main loop -- stale operands, timing decomposition only)
-#endif
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = JS; j < TN; ++j) {
@@ -836,46 +773,14 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                     if constexpr (EPI == 1) MmaFrag<T>::mma(acc[i][j], bj, fa[cur][i]);
                     else MmaFrag<T>::mma(acc[i][j], fa[cur][i], bj);
                 }
-                if (ROT) {
-                    load_b(0, j, nB + j * 4096);
-#if !RF_SPREAD_DMA
-                    __builtin_amdgcn_sched_barrier(0);
-#endif
-                }
-#if RF_SPREAD_DMA
-                // the pieces of tile kt+2 go out between the MFMA columns of k-step 3 (their issue slots hide under the matrix pipe) instead of
-                // in one burst behind the barrier, where both waves of a SIMD stall on ~9 x 60-180 issue cycles at the same time
-#if RF_SPREAD_DMA == 3
-                // ... in thirds: behind the barrier of k-step 3, then at k-steps 0 and 1 of the next tile (stage ^ 1 there: the stage that tile's
-                // predecessor freed); the issue state advances after k-step 1
-                if (kk != 2) {
-                    constexpr int G = kk == 3 ? 0 : (kk == 0 ? 1 : 2), gs = G * NP / 3, gn = (G + 1) * NP / 3 - gs, COLS = TN - JS;
-                    const int q0 = gs + (j - JS) * gn / COLS, q1 = gs + (j - JS + 1) * gn / COLS;          // (constants after unrolling)
-                    if (q1 > q0 && !RF_DBG(p, 32)) {
-                        if (kk == 3) { if (more) issue_pieces(stage, q0, q1); }
-                        else if (cont) issue_pieces(stage ^ 1, q0, q1);
-                    }
-                }
-                if (ROT || kk != 2) __builtin_amdgcn_sched_barrier(0);
-#elif RF_SPREAD_DMA == 4
-                // 8-wave blocks: the waves that share a SIMD issue at different times -- waves 0-3 behind the barrier of k-step 3 (tile kt+2 into
-                // the stage just freed), waves 4-7 at k-step 0 of the next tile (`cont`: into stage ^ 1) -- so that one wave of every SIMD feeds
-                // the matrix pipe while the other is stalled on the address path
-                if (kk == 3 || kk == 0) {
-                    constexpr int COLS = TN - JS, PPC = (NP + COLS - 1) / COLS;
-                    const int q0 = (j - JS) * PPC, q1 = (j - JS + 1) * PPC < NP ? (j - JS + 1) * PPC : NP;
-                    if (kk == 3) { if (more && !late) issue_pieces(stage, q0, q1); }
-                    else if (cont && late) issue_pieces(stage ^ 1, q0, q1);
-                }
-                if (ROT || kk == 3 || kk == 0) __builtin_amdgcn_sched_barrier(0);
-#else
+                if (ROT) load_b(0, j, nB + j * 4096);
+                // the pieces of tile kt+2 ('more': it exists) go out between the MFMA columns of k-step 3 (their issue slots hide under the matrix
+                // pipe) instead of in one burst behind the barrier, where both waves of a SIMD stall on ~9 x 60-180 issue cycles at the same time
                 if (kk == 3) {
                     constexpr int COLS = TN - JS, PPC = (NP + COLS - 1) / COLS;
-                    if (more && !RF_DBG(p, 32)) issue_pieces(stage, (j - JS) * PPC, (j - JS + 1) * PPC < NP ? (j - JS + 1) * PPC : NP);
+                    if (more) issue_pieces(stage, (j - JS) * PPC, (j - JS + 1) * PPC < NP ? (j - JS + 1) * PPC : NP);
                 }
                 if (ROT || kk == 3) __builtin_amdgcn_sched_barrier(0);
-#endif
-#endif
             }
             __builtin_amdgcn_sched_barrier(0);
         };
@@ -899,8 +804,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                 issue_pieces(1, 0, NP);
                 if (nk > 2) next_tile();
                 if constexpr (W8) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // tile 1 may have had no W pieces: no fixed count
-                else if (RF_DBG(p, 128)) {}          // timing decomposition: the first tile is not waited for (upper bound of what a tile loop that
-                                                      // issues the next tile's first pieces ahead of the epilogue could hide)
                 else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(HX ? BV : NP) : "memory");          // (HX: tile 1 -- filter column 1 -- has W pieces only)
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -914,11 +817,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
 #pragma unroll
             for (int j = 0; j < TN; ++j) load_b(0, j, curB + j * 4096 + (fkb[0] ^ curPar));
         }
-#if RF_RES_TOUCH
-        // (the touch loads are older than every piece: the prologue's wait covered them; their registers are free from here on)
-        if (nk == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("" ::"v"(touch_[0]), "v"(touch_[1]), "v"(touch_[2]), "v"(touch_[3]));
-#endif
         if constexpr (NST > 2) {
             // ring of NST stages: tile kt is multiplied out of stage kt % NST while tiles kt+1 .. kt+NST-1 are in LDS or in flight; the
             // stage it frees takes tile kt+NST.  For launches of at most one block per CU, where no second block covers the latency
@@ -941,28 +839,11 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
         for (int kt = 0; kt < nk; ++kt) {
             const int stage = kt & 1;
             const bool more = kt + 2 < nk;
-#if RF_SPREAD_DMA == 4
-            const bool cont = kt >= 1 && kt + 1 < nk;          // late waves: tile kt+1 is still to be issued (k-step 0)
-            phase(integral_constant<int, 0>{}, stage, more, false, cont);
-            if (late && kt >= 1 && kt + 2 < nk) next_tile();
-            phase(integral_constant<int, 1>{}, stage, more, false);
-            phase(integral_constant<int, 2>{}, stage, more, false);
-            phase(integral_constant<int, 3>{}, stage, more, false);
-            if (!late && kt + 3 < nk) next_tile();
-#elif RF_SPREAD_DMA == 3
-            const bool cont = kt >= 1 && kt + 1 < nk;          // tile kt+1's second and third thirds are still to be issued
-            phase(integral_constant<int, 0>{}, stage, more, false, cont);
-            phase(integral_constant<int, 1>{}, stage, more, false, cont);
-            if (kt >= 1 && kt + 2 < nk) next_tile();
-            phase(integral_constant<int, 2>{}, stage, more, false);
-            phase(integral_constant<int, 3>{}, stage, more, false);
-#else
             phase(integral_constant<int, 0>{}, stage, more, false);
             phase(integral_constant<int, 1>{}, stage, more, false);
             phase(integral_constant<int, 2>{}, stage, more, false);
             phase(integral_constant<int, 3>{}, stage, more, false);
             if (kt + 3 < nk) next_tile();
-#endif
             const char* t = curA; curA = othA; othA = t;
             if constexpr (HX) {          // the tile multiplied next becomes current; its successor: next filter column, or column 0 of the next group's stage
                 if (++m_dx == 3) { m_dx = 0; m_st ^= 1; }
@@ -995,162 +876,6 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
         }
     }
 
-    if (RF_DBG(p, 1)) {          // timing experiment: no epilogue (keep the accumulators observable)
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) t += acc[i][j][0];
-        if (t == 123.456f) ((float*)p.out)[0] = t;
-        return;
-    }
-    if constexpr (EPI == 2) {
-        // ---- packed staged epilogue (bf16 output).  The chunked fp32 staging of the general path keeps 6 of 8 waves idle while two
-        // write 80 KB of LDS with 4-byte stores, four times per tile (15 us of a 256x320 tile's 27 us at K = 320, RF_GEMM_DBG
-        // decomposition r02c).  Here bias / timestep vector / activation / GEGLU happen in registers (a lane owns ONE column per
-        // 32-column block), neighbouring lanes exchange one value by DPP so that each holds a (col 2c, col 2c+1) bf16 pair of
-        // alternating rows, and ALL waves write the whole tile as bf16 [BM][BNo] in one pass (half the LDS bytes: a 256x320 tile is
-        // exactly the 160 KB of LDS).  One barrier later every thread streams 16-byte row segments: residual add (fp32),
-        // GroupNorm partial sums of the values as stored, 16-byte global stores.  Host guarantees: N % 16 == 0, 16-byte aligned
-        // rows, no split-K, no PReLU, per-tile uniform timestep vector.
-        bool geglu = false;
-        if constexpr (TN % 2 == 0) geglu = p.act == RF_ACT_GEGLU;
-        const int BNo = geglu ? BN / 2 : BN;                 // columns of the staged tile
-        char* const tile = smem;
-        TO* const outp = (TO*)p.out + zb * p.sO;
-        const TO* const resp = p.residual ? (const TO*)p.residual + zb * p.sR : nullptr;
-        const float* const rvu = p.rowvec ? p.rowvec + (long long)(m0 / p.rows_per_sample) * p.ldv : nullptr;
-        const int odd = lane & 1;
-        // phase 1: registers -> bf16 tile
-        auto stage_block = [&](const float* y, int rowb, int colb) {
-            // y[16]: this lane's column of a 32x32 block (rows (r&3) + 8*(r>>2) + 4*lhalf); rowb / colb: block origin in the tile
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const float send = odd ? y[r] : y[r + 1];            // what the neighbour lane (col ^ 1) needs
-                const float keep = odd ? y[r + 1] : y[r];
-                const float got = as_f32((uint32_t)__builtin_amdgcn_mov_dpp((int)as_u32(send), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-                const uint32_t w = odd ? pack_bf2(got, keep) : pack_bf2(keep, got);       // (col 2c, col 2c+1)
-                const int row = rowb + (r & 3) + 8 * (r >> 2) + 4 * lhalf + odd;        // even lanes: row of r, odd lanes: row of r+1
-                *(uint32_t*)(tile + (row * BNo + colb + (lrow & ~1)) * 2) = w;
-            }
-        };
-        if (geglu) {
-            if constexpr (TN % 2 == 0) {
-#pragma unroll
-                for (int j = 0; j < TN; j += 2) {
-                    const int cv = n0 + (wn * TN + j) * 32 + lrow;
-                    const float bv = (p.bias && cv < p.N) ? p.bias[cv] : 0.f, bg = (p.bias && cv + 32 < p.N) ? p.bias[cv + 32] : 0.f;
-#pragma unroll
-                    for (int i = 0; i < TM; ++i) {
-                        float y[16];
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) y[r] = (acc[i][j][r] * p.alpha + bv) * gelu_for<T>(acc[i][j + 1][r] * p.alpha + bg);
-                        stage_block(y, (wm * TM + i) * 32, ((wn * TN + j) >> 1) * 32);
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int col = n0 + (wn * TN + j) * 32 + lrow;
-                float cadd = 0.f;
-                if (col < p.N) {
-                    if (p.bias) cadd = p.bias[col];
-                    if (rvu) cadd += rvu[col];
-                }
-#pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    float y[16];
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) y[r] = acc[i][j][r] * p.alpha + cadd;       // (host: act is NONE or GEGLU on this path --
-                                                                                            // an unrolled 5-way activation chain per value
-                                                                                            // is 24 k instructions, beyond the I-cache)
-                    stage_block(y, (wm * TM + i) * 32, (wn * TN + j) * 32);
-                }
-            }
-        }
-        lds_barrier();
-        // phase 2: thread -> one fixed 8-column segment, every EROWS-th row
-        const int VPR8 = BNo / 8;                        // 16-byte segments per row
-        const int EROWS = NT / VPR8;
-        const int cs = tid % VPR8, er = tid / VPR8;
-        const int ncol0 = geglu ? (n0 >> 1) : n0, Nout = geglu ? (p.N >> 1) : p.N;
-        const int cl = cs * 8, col = ncol0 + cl;
-        const bool t_on = er < EROWS && col < Nout;
-        const bool gn_on = p.gn_rows > 0;
-        float gsum[8], gsq[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) gsum[e] = gsq[e] = 0.f;
-        constexpr int U = 4;                              // rows of residual loads in flight
-        for (int rl0 = er; rl0 < BM; rl0 += U * EROWS) {
-            u32x4_t rq[U], sv[U];
-            bool ok[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int rl = rl0 + u * EROWS, row = m0 + rl;
-                ok[u] = t_on && rl < BM && row < p.M;
-                if (ok[u]) {
-                    if (resp) rq[u] = *(const u32x4_t*)(resp + (long long)row * p.ldr + col);
-                    sv[u] = *(const u32x4_t*)(tile + (rl * BNo + cl) * 2);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (!ok[u]) continue;
-                const int row = m0 + rl0 + u * EROWS;
-                u32x4_t w = sv[u];
-                if (resp) {
-                    float a[8], b[8];
-                    unpack16<bf16_t>(sv[u], a);
-                    unpack16<bf16_t>(rq[u], b);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) a[e] += b[e];
-                    w = pack16<bf16_t>(a);
-                }
-                if (gn_on) {
-                    float a[8];
-                    unpack16<bf16_t>(w, a);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { gsum[e] += a[e]; gsq[e] += a[e] * a[e]; }
-                }
-                if (RF_DBG(p, 4)) {          // experiment: two 8-byte stores instead of one 16-byte store
-                    u32x2_t* d2 = (u32x2_t*)(outp + (long long)row * p.ldo + col);
-                    d2[0] = u32x2_t{w[0], w[1]};
-                    d2[1] = u32x2_t{w[2], w[3]};
-                } else if (!(RF_DBG(p, 8))) {
-                    *(u32x4_t*)(outp + (long long)row * p.ldo + col) = w;
-                }
-            }
-        }
-        if (gn_on) {
-            // column sums of the tile: [EROWS][BNo] per-thread partials -> 32 group sums per consumer -> one chunk slot (fp64)
-            lds_barrier();                                 // every thread is done with the staged tile
-            float* const csum = (float*)smem;              // [2][EROWS][BNo]
-            if (er < EROWS) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    csum[er * BNo + cl + e] = gsum[e];
-                    csum[(EROWS + er) * BNo + cl + e] = gsq[e];
-                }
-            }
-            lds_barrier();
-            if (tid < 64) {
-                const int c = tid >> 5, g = tid & 31;
-                if (p.gn_part[c]) {
-                    const int cpg = p.gn_cpg[c], base = p.gn_coff[c] + n0;            // consumer channel of local column 0
-                    const int lo = max(0, g * cpg - base), hi = min(min(BN, p.N - n0), (g + 1) * cpg - base);
-                    double sa = 0.0, sq = 0.0;
-                    for (int k = lo; k < hi; ++k)
-                        for (int r = 0; r < EROWS; ++r) { sa += (double)csum[r * BNo + k]; sq += (double)csum[(EROWS + r) * BNo + k]; }
-                    const int b = m0 / p.gn_rows, mt = (m0 - b * p.gn_rows) / BM;
-                    double* o = p.gn_part[c] + (((long long)b * p.gn_nch[c] + p.gn_slot[c] + mt * p.tiles_n + tile_n) * 32 + g) * 2;
-                    o[0] = sa;
-                    o[1] = sq;
-                }
-            }
-        }
-        return;
-    }
     if constexpr (EPI == 1) {
         // ---- direct epilogue: lane (row lrow of its 32-row block, half lhalf) holds columns 16*lhalf .. 16*lhalf+15 of every
         // 32-column block of its wave tile.  Host guarantees (launch_typed): N % 16 == 0, 16-byte aligned rows of out / residual /
@@ -1174,19 +899,17 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
         const TO* const resp = p.residual ? (const TO*)p.residual + zb * p.sR : nullptr;
         constexpr int OV = sizeof(TO) == 2 ? 2 : 4;      // 16-byte vectors per 16 output values
         auto store16 = [&](TO* dst, const float* v) {
-            if (RF_DBG(p, 8)) return;                                                          // experiment: no global stores
-            if (RF_DBG(p, 16)) dst = (TO*)p.out + (((dst - (TO*)p.out) * (long long)sizeof(TO)) & 0xFFFFF) / (long long)sizeof(TO);   // experiment: all stores into 1 MB
             if constexpr (sizeof(TO) == 2) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     u32x4_t w;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) w[e] = pack2<TO>(v[8 * h + 2 * e], v[8 * h + 2 * e + 1]);
-                    st16_out((u32x4_t*)dst + h, w);
+                    ((u32x4_t*)dst)[h] = w;
                 }
             } else {
 #pragma unroll
-                for (int h = 0; h < 4; ++h) st16_out((u32x4_t*)dst + h, u32x4_t{as_u32(v[4 * h]), as_u32(v[4 * h + 1]), as_u32(v[4 * h + 2]), as_u32(v[4 * h + 3])});
+                for (int h = 0; h < 4; ++h) ((u32x4_t*)dst)[h] = u32x4_t{as_u32(v[4 * h]), as_u32(v[4 * h + 1]), as_u32(v[4 * h + 2]), as_u32(v[4 * h + 3])};
             }
         };
         // column constants -> LDS (the main loop ended on a barrier: the operand stages are dead)
@@ -1295,10 +1018,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
             // flight.  sched_barrier(0) after every block keeps hipcc from hoisting every load of the unrolled nest to the top (the 2x5
             // wave tile then spills ~170 registers per lane).
             constexpr int NBLK = TM * TN;
-#ifndef RF_EPI_PFD
-#define RF_EPI_PFD 4
-#endif
-            constexpr int PFD = sizeof(TO) == 2 ? (NBLK < RF_EPI_PFD ? NBLK : RF_EPI_PFD) : 2;      // residual blocks in flight (8 / 16 registers each): the
+            constexpr int PFD = sizeof(TO) == 2 ? (NBLK < 4 ? NBLK : 4) : 2;      // residual blocks in flight (8 / 16 registers each): the
                                                                                   // fragment registers of the main loop are free now
             u32x4_t rq[PFD][OV];
             auto load_res = [&](int blk, u32x4_t* r) {
@@ -1357,7 +1077,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                                 for (int e = 0; e < E; ++e) v[e] = acc[i][j][h * E + e] * p.alpha + cb[(h * E + e) >> 2][(h * E + e) & 3] + (resp ? f[e] : 0.0f);
                             }
                             const u32x4_t w = pack16<TO>(v);
-                            if (!(RF_DBG(p, 8))) st16_out((u32x4_t*)dst + h, w);
+                            ((u32x4_t*)dst)[h] = w;
                             if (keep_on) {
                                 float y[E];
                                 unpack16<TO>(w, y);              // the values as stored replace the (dead) accumulators: no extra registers
@@ -1960,15 +1680,13 @@ static int launch_cfg(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hipS
         // (large images); strips along M (pn = 1) keep a W panel there -- at the 8x8 / 16x16 levels W is the big operand and N-fastest makes every
         // XCD stream ALL of it (1024 x 1280 x 11520: 239 MB instead of 69 MB through the fabric); wide layers at the 32x32 / 16x16 levels (GEGLU
         // 16384 x 5120 x 640: 20 W panels of 327 KB) want both bounded.
-        static const int pm_env = tune_env("RF_GEMM_PM", 0), pn_env = tune_env("RF_GEMM_PN", 0), patch_on = tune_env("RF_GEMM_PATCH", 1);
-        static const int mf_env = tune_env("RF_GEMM_MFAST", -1);
         const long long tiles = (long long)p.tiles_m * p.tiles_n, run = (tiles + 7) / 8;
         const double a_panel = (double)BM * (conv ? p.Ctot : p.K) * sizeof(T), w_panel = (double)BN * p.K * (W8 ? 1 : (int)sizeof(T));
         // strips: the panels a run touches (the rule of rounds 2-4, kept as it was: every split-K and two-blocks-per-CU launch was tuned on it)
         const double n_mx = (double)((run + p.tiles_n - 1) / p.tiles_n + (run % p.tiles_n ? 1 : 0)), n_nx = (double)(run < p.tiles_n ? run : p.tiles_n);
         const double m_mx = (double)(run < p.tiles_m ? run : p.tiles_m), m_nx = (double)((run + p.tiles_m - 1) / p.tiles_m + (run % p.tiles_m ? 1 : 0));
         const double cost_n = n_mx * a_panel + n_nx * w_panel, cost_m = m_mx * a_panel + m_nx * w_panel;
-        const bool mfast = mf_env >= 0 ? mf_env != 0 : cost_m < 0.8 * cost_n;
+        const bool mfast = cost_m < 0.8 * cost_n;
         int pm = mfast ? p.tiles_m : 1, pn = mfast ? 1 : p.tiles_n;
         // patches: only launches of several rounds of one 8-wave block per CU without split-K (measured, profiles/r05c_tile_order_fetch.txt: GEGLU
         // 16384 x 5120 x 640 296 -> 169 MB of fabric reads per launch, 4096 x 10240 x 1280 284 -> 243 MB and 129 -> 125 us, 4096 x 1280 x 5760
@@ -1977,11 +1695,8 @@ static int launch_cfg(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hipS
         // along N -- the pm A panels stay resident if they fit beside the patch's pn W panels, the W panels are streamed once per super-row.
         // (bf16 / fp32 operands only: the fp8 x fp8 and fp8-weight kernels of configs[4] LOSE 3 % per batch on the same rule -- half the operand bytes per tile, other
         //  tile shapes; profiles/r05r_r04_vs_r05_same_box.txt)
-#ifndef RF_PATCH_FP8
-#define RF_PATCH_FP8 0          // (experiment builds: 1 applies the patch order to the fp8 / fp8-weight kernels too -- the A/B of profiles/r06f)
-#endif
-        constexpr bool PATCH_T = RF_PATCH_FP8 || (!W8 && !std::is_same<T, fp8_t>::value);
-        if (PATCH_T && patch_on && p.splitk == 1 && WM * WN == 8 && tiles >= 2 * 256 && mf_env < 0) {
+        constexpr bool PATCH_T = !W8 && !std::is_same<T, fp8_t>::value;
+        if (PATCH_T && p.splitk == 1 && WM * WN == 8 && tiles >= 2 * 256) {
             const double conc = 32.0, cap = 3.0 * 1024 * 1024;          // tiles in flight per XCD; L2 bytes the operands may take (4 MB minus output lines)
             auto cost_of = [&](int h, int w) {
                 const double nsr = (double)run / ((double)h * p.tiles_n) < 1.0 ? 1.0 : (double)run / ((double)h * p.tiles_n);          // super-rows per run
@@ -2000,15 +1715,13 @@ static int launch_cfg(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hipS
                 if (c < 0.6 * best) { pm = h; pn = w; best = c / 0.6; }
             }
         }
-        if (pm_env > 0 && pn_env > 0) { pm = pm_env < p.tiles_m ? pm_env : p.tiles_m; pn = pn_env < p.tiles_n ? pn_env : p.tiles_n; }
         p.pm = pm;
         p.pn = pn;
     }
     // Split-K through fragment-ordered slabs (direct-epilogue kernels + splitk_reduce_frag_kernel): wherever the reduce pass has nothing to do
     // but alpha / bias / per-sample vector / residual (+ statistics) on 16-byte aligned rows
-    static const int frag_env = tune_env("RF_SK_FRAG", 1);
     constexpr bool FRAG_OK = (WM * WN == 8) || (TM * TN == 5) || (TM * TN >= 16) || std::is_same<T, fp8_t>::value;      // (= DIRECT_OK below)
-    const bool frag = FRAG_OK && frag_env && p.splitk > 1 && p.glds && p.epi2_ok && d->act == RF_ACT_NONE && !p.oscale && d->batch == 1 &&
+    const bool frag = FRAG_OK && p.splitk > 1 && p.glds && p.epi2_ok && d->act == RF_ACT_NONE && !p.oscale && d->batch == 1 &&
                       (long long)p.splitk * p.tiles_m * p.tiles_n * BM * BN * 4 <= d->workspace_bytes;
     // statistics tiling: the GEMM tile, or the reduce pass's tile when split-K moves the epilogue there
     const int skr = sk_rows_for(p.M, p.N);
@@ -2020,16 +1733,13 @@ static int launch_cfg(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hipS
                  "rf_conv_gemm: fp8 output needs the direct epilogue (even TN, aligned rows, no split-K) -- this launch got a %d x %d tile", BM, BN);
     }
     // epilogue form (needed by the plan query too): see the selection notes below
-    static const int epi_env = tune_env("RF_EPI", -1);
-    constexpr bool PACKED_OK = std::is_same<TO, bf16_t>::value && !A8;
     constexpr bool DIRECT_OK = (WM * WN == 8) || (TM * TN == 5) || (TM * TN >= 16) || std::is_same<T, fp8_t>::value;      // (fp8 x fp8: every tile --
                                                                                           // the GEGLU epilogue with fp8 output exists only in this form)
     const bool ep_common = p.glds && p.epi2_ok && p.splitk == 1 && (!p.rowvec || p.rows_per_sample % BM == 0) &&
                            (d->act == RF_ACT_NONE || (d->act == RF_ACT_GEGLU && TN % 2 == 0));
-    static const int gn_direct = tune_env("RF_EPI_GN", 1);      // 0: fused statistics keep EPI 0
-    const bool direct = DIRECT_OK && (epi_env < 0 || epi_env == 1) && ep_common && (p.gn_rows == 0 || (gn_direct && d->act == RF_ACT_NONE));
+    const bool direct = DIRECT_OK && ep_common && (p.gn_rows == 0 || d->act == RF_ACT_NONE);
     RF_CHECK(!hx || (HX_OK && conv && p.glds && p.KH == 3 && p.KW == 3 && p.stride == 1 && !p.ups && p.pad_t == 1 && p.pad_l == 1 && p.Hin == p.Hout &&
-                     p.Win == p.Wout && p.Wout >= 16 && BM % p.Wout == 0 && (BM / p.Wout) * (p.Wout + 2) <= AXR_ && epi_env != 2 &&
+                     p.Win == p.Wout && p.Wout >= 16 && BM % p.Wout == 0 && (BM / p.Wout) * (p.Wout + 2) <= AXR_ &&
                      !(DEEP_OK && (long long)p.tiles_m * p.tiles_n * p.splitk <= 256)),
              "rf_conv_gemm: korder 2 (row-extended A tiles) needs a bf16 3x3 stride-1 pad-1 convolution, Wout >= 16, whose %d-row tile holds whole image rows (Wout = %d) "
              "and that does not take the 4-stage ring", BM, p.Wout);
@@ -2056,45 +1766,37 @@ static int launch_cfg(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hipS
                      "rf_conv_gemm: GroupNorm consumer %d: cpg=%d slot=%d needs %d slots of %d", c, p.gn_cpg[c], p.gn_slot[c], need, p.gn_nch[c]);
     }
     dim3 grid(p.tiles_m * p.tiles_n, d->batch, p.splitk), block(WM * WN * 64);
-    // Epilogue selection (RF_GEMM_DBG decomposition + tools/bench_gemm.py A/B, r02c: the chunked fp32 staging costs 47 us of the 84 us
+    // Epilogue selection (timing decomposition + tools/bench_gemm.py A/B, r02c: the chunked fp32 staging costs 47 us of the 84 us
     // of the 65536x960x320 qkv GEMM).
     //   EPI 1, direct register -> global row segments: no LDS pass, no barriers; fastest wherever nothing needs the tile as a whole
     //          (qkv 86 -> 59 us, proj 33 -> 24, ff2 62 -> 52, GEGLU 196 -> 164).  8-wave tiles and the 128x160 tile.
-    //   EPI 2, bf16 tile staged in ONE pass by all waves (packed pairs): carries the fused GroupNorm statistics (bf16 output).
     //   EPI 0, fp32 tile staged in row chunks: everything else (split-K partials, per-row timestep vectors, activations other than
     //          GEGLU, fp32 output with statistics, unaligned shapes).
-    // RF_EPI=0 forces EPI 0, RF_EPI=1 / 2 allow only that fast form (A/B runs).
-    // (packed: measured neutral-to-negative in situ -- proj_out 4096x1280x1280 with fused statistics 37 -> 63 us, the rest within
-    //  noise, r02f -- so it is opt-in: RF_EPI=2)
-    const bool packed = !direct && PACKED_OK && epi_env == 2 && ep_common;
     RF_CHECK(!p.oscale || direct, "rf_conv_gemm: fp8 output needs the direct epilogue (8-wave tile, aligned rows, no split-K)");
-    constexpr int smem_pk = BM * BN * 2;
-    const int smem_l = (packed && smem_pk > smem) ? smem_pk : smem;
 #define RF_LAUNCH_VARIANT_X(CONV_, GLDS_, EPI_, LNF_, HX_)                                                                      \
     {                                                                                                                            \
-        constexpr int E_ = (EPI_ == 2 && PACKED_OK) ? 2 : ((EPI_ == 1 && DIRECT_OK) ? 1 : 0);                                   \
+        constexpr int E_ = (EPI_ == 1 && DIRECT_OK) ? 1 : 0;                                                                     \
         if (GLDS_ && deep) {                                                                                                     \
             auto k = conv_gemm_kernel<T, TO, WM, WN, TM, TN, CONV_, GLDS_, (GLDS_ ? NSTD : 2), E_, (W8 && GLDS_), LNF_, false>; \
             RF_RAISE_LDS(k, smem_deep, "rf_conv_gemm");                                                                          \
             hipLaunchKernelGGL(k, grid, block, smem_deep, st, p);                                                                \
         } else {                                                                                                                 \
             auto k = conv_gemm_kernel<T, TO, WM, WN, TM, TN, CONV_, GLDS_, (GLDS_ ? NST : 2), E_, (W8 && GLDS_), LNF_, HX_>;    \
-            constexpr int SM_ = HX_ ? smem_hx : (smem_pk > smem ? smem_pk : smem);                                               \
+            constexpr int SM_ = HX_ ? smem_hx : smem;                                                                            \
             RF_RAISE_LDS(k, SM_, "rf_conv_gemm");                                                                                \
-            hipLaunchKernelGGL(k, grid, block, HX_ ? smem_hx : smem_l, st, p);                                                   \
+            hipLaunchKernelGGL(k, grid, block, SM_, st, p);                                                                      \
         }                                                                                                                        \
     }
 #define RF_LAUNCH_VARIANT_LN(CONV_, GLDS_, EPI_, LNF_) RF_LAUNCH_VARIANT_X(CONV_, GLDS_, EPI_, LNF_, false)
 #define RF_LAUNCH_VARIANT(CONV_, GLDS_, EPI_) RF_LAUNCH_VARIANT_LN(CONV_, GLDS_, EPI_, 0)
-    const int esel = packed ? 2 : ((direct || frag) ? 1 : 0);
+    const int esel = (direct || frag) ? 1 : 0;
     // The ring of four stages for 128x160 launches of at most one block per CU (4096 x 1280 x K <= 6000: the projections, ff.net.2 and 1x1 skips
     // of the 16x16 level, 25 launches per step): nothing else covers the single tile of look-ahead there.  Alone (warm weights) it is neutral
     // (4096x1280x5120 68.3 -> 66.7 us); in situ, where every launch streams weights the previous ones pushed out of the caches, -0.9 % per batch
     // (tools/archive/exp_r03_10.sh: 921.7 -> 913.5 ms, same box, two runs each).  Forcing the 8x8 level (M = 1024) onto this tile + ring: neutral for the
     // 3x3 convs, +0.9 % for its small projections.
-    static const int deep_env = tune_env("RF_GEMM_DEEP", 256);        // largest grid (blocks) that takes the ring
     constexpr int smem_deep = NSTD * (BM + BN) * 128 > smem ? NSTD * (BM + BN) * 128 : smem;
-    const bool deep = DEEP_OK && p.glds && !packed && !p.x3 && !hx && (long long)grid.x * grid.y * grid.z <= deep_env;
+    const bool deep = DEEP_OK && p.glds && !p.x3 && !hx && (long long)grid.x * grid.y * grid.z <= 256;
     if constexpr (A8) {            // fp8 activations: direct-to-LDS kernels only, staged or direct epilogue
         if (conv) { if (esel == 1) RF_LAUNCH_VARIANT(true, true, 1) else RF_LAUNCH_VARIANT(true, true, 0) }
         else { if (esel == 1) RF_LAUNCH_VARIANT(false, true, 1) else RF_LAUNCH_VARIANT(false, true, 0) }
@@ -2106,14 +1808,12 @@ static int launch_cfg(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hipS
                 else RF_LAUNCH_VARIANT_X(true, true, 0, 0, true)
             }
         }
-        else if (esel == 2) RF_LAUNCH_VARIANT(true, true, 2)
         else if (esel == 1) RF_LAUNCH_VARIANT(true, true, 1)
         else RF_LAUNCH_VARIANT(true, true, 0)
     } else if (conv) {
         RF_LAUNCH_VARIANT(true, false, 0)
     } else if (p.glds) {
-        if (esel == 2) RF_LAUNCH_VARIANT(false, true, 2)
-        else if (esel == 1) {
+        if (esel == 1) {
             // (LayerNorm roles: compile-time variants of the direct epilogue, bf16 linear layers only)
             if constexpr (LN_OK) {
                 if (p.ln_in) RF_LAUNCH_VARIANT_LN(false, true, 1, 2)
@@ -2140,14 +1840,6 @@ static int launch_cfg(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hipS
     return 0;
 }
 
-#ifdef RF_EXPERIMENT
-template <typename T, typename TO, int TN_, bool W8>
-static int launch_wide(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hipStream_t st) {
-    if constexpr (!W8 && sizeof(T) == 2 && sizeof(TO) == 2) return launch_cfg<T, TO, 2, 2, 4, TN_, false>(d, p, conv, st);
-    else { RF_CHECK(false, "rf_conv_gemm: the one-wave-per-SIMD tiles are bf16 -> bf16 experiments"); }
-}
-#endif
-
 template <typename T, typename TO, bool W8 = false>
 static int launch_typed(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hipStream_t st) {
     if constexpr (std::is_same<T, fp8_t>::value) {
@@ -2168,30 +1860,6 @@ static int launch_typed(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hi
         return launch_cfg<T, TO, 2, 2, 2, 2, false>(d, p, conv, st);
     } else {
     const int N = p.N;
-    {   // experiments: RF_GEMM_CFG=<0..6> forces one tile configuration (GEGLU still needs an even TN)
-        static const int forced_all = tune_env("RF_GEMM_CFG", -1);
-        static const int small_k = tune_env("RF_SMALLK_K", 0);          // K <= this ...
-        static const int small_cfg = tune_env("RF_SMALLK_CFG", -1);     // ... uses this config
-        static const int m_exact = tune_env("RF_MCFG_M", 0);               // M == this ...
-        static const int m_cfg = tune_env("RF_MCFG_CFG", -1);              // ... uses this config
-        const int forced = forced_all >= 0 ? forced_all : (p.M == m_exact ? m_cfg : (p.K <= small_k ? small_cfg : -1));
-        const bool g = d->act == RF_ACT_GEGLU;
-        switch (forced) {
-            case 0: if (!g && p.glds && d->batch == 1) return launch_cfg<T, TO, 4, 2, 2, 5, W8>(d, p, conv, st); break;
-            case 1: if (p.glds && d->batch == 1) return launch_cfg<T, TO, 4, 2, 2, 4, W8>(d, p, conv, st); break;
-            case 2: if (!g && p.glds && d->batch == 1) return launch_cfg<T, TO, 4, 2, 1, 5, W8>(d, p, conv, st); break;
-            case 3: if (p.glds && d->batch == 1) return launch_cfg<T, TO, 4, 2, 1, 4, W8>(d, p, conv, st); break;
-            case 4: return launch_cfg<T, TO, 2, 2, 2, 2, W8>(d, p, conv, st);
-            case 5: return launch_cfg<T, TO, 4, 1, 1, 2, W8>(d, p, conv, st);
-            case 6: if (!g) return launch_cfg<T, TO, 4, 1, 1, 5, W8>(d, p, conv, st); break;
-#ifdef RF_EXPERIMENT
-            // one wave per SIMD, 512 registers per lane: 4 waves as 2 x 2 with 128x160 / 128x128 wave tiles (a third fewer fragment reads per FLOP)
-            case 7: if (!g && p.glds && d->batch == 1) return launch_wide<T, TO, 5, W8>(d, p, conv, st); break;
-            case 8: if (p.glds && d->batch == 1) return launch_wide<T, TO, 4, W8>(d, p, conv, st); break;
-#endif
-            default: break;
-        }
-    }
     // 8-wave blocks with 320- / 256-wide tiles: half the LDS and L2 traffic per FLOP of the 4-wave configs.  Take the tallest
     // tile (256 rows, wave tile 64 x 160 / 64 x 128) that still gives ~one block per CU, else the 128-row variant.
     if (p.glds && d->batch == 1) {
@@ -2219,12 +1887,11 @@ static int launch_typed(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hi
                 // the 16x16 level: 640 tiles = 2.5 rounds, three round times -- are split along N: the whole rounds on 256-row tiles, the columns of
                 // the partial round as a second launch, which this dispatcher gives 128-row tiles (one full round of half-size tiles).  Launches
                 // that carry nothing tile-numbered (no fused GroupNorm statistics, no LayerNorm producer role, no fp8 output, one W).
-                static const int tail_on = tune_env("RF_TAIL_SPLIT", 1);
                 const long long tiles_ = mt256 * nt, full_ = tiles_ / 256, rem_ = tiles_ - full_ * 256;
                 // (... and whose tail still fills the chip with 8-wave 128-row tiles: smaller tails fall to 4-wave tiles without the direct epilogue a
                 //  LayerNorm consumer needs)
                 const long long tail_nt_ = full_ >= 1 && mt256 > 0 ? nt - full_ * 256 / mt256 : 0;
-                if (tail_on && !n320 && full_ >= 1 && rem_ * 5 >= 256 && rem_ * 5 <= 3 * 256 && (full_ * 256) % mt256 == 0 && mt128 * tail_nt_ >= 192 && p.gn_rows == 0 && !p.ln_out && !p.oscale &&
+                if (!n320 && full_ >= 1 && rem_ * 5 >= 256 && rem_ * 5 <= 3 * 256 && (full_ * 256) % mt256 == 0 && mt128 * tail_nt_ >= 192 && p.gn_rows == 0 && !p.ln_out && !p.oscale &&
                     !p.w_ps && !p.x3 && d->batch == 1 && (d->act == RF_ACT_NONE || d->act == RF_ACT_GEGLU)) {
                     const int n1 = (int)(full_ * 256 / mt256) * 256;                       // columns of the whole rounds
                     auto part = [&](int n_off, int n_len) {
@@ -2263,15 +1930,13 @@ static int launch_typed(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hi
                 return n320 ? launch_cfg<T, TO, 4, 2, 2, 5, W8>(d, p, conv, st) : launch_cfg<T, TO, 4, 2, 2, 4, W8>(d, p, conv, st);
             }
             // K up to ~90 tiles: two co-resident 4-wave 128x160 blocks per CU (each other's prologue / epilogue cover) beat one
-            // 8-wave 128x320 block in situ (sweep: -1.2 % per batch at 6000, worse again from 11520); RF_SHORTK overrides.  Also when K is
+            // 8-wave 128x320 block in situ (sweep: -1.2 % per batch at 6000, worse again from 11520).  Also when K is
             // too short for split-K to bring the 128x320 grid to size (4096 x 1280 x 1280: 23 us, against 26 us on 128x128 tiles).
-            static const int shortk = tune_env("RF_SHORTK", 6000);
-            if (n320 && p.K <= shortk && mt128 * (N / 160) >= 256) return launch_cfg<T, TO, 4, 1, 1, 5, W8>(d, p, conv, st);
+            if (n320 && p.K <= 6000 && mt128 * (N / 160) >= 256) return launch_cfg<T, TO, 4, 1, 1, 5, W8>(d, p, conv, st);
             // 64-128 tiles of 256 rows (the 3x3 convs of the 16x16 level, the long-K N = 640 convs of the 32x32 level): split-K 2-4 over the
             // 256-row tiles rather than 128-row tiles -- the 64x160 wave tile's main loop runs 1.0-1.25 PF where the 32x160 one stays below
             // 0.95 (6 KB of fragment reads per 5 MFMAs), and the fragment-ordered slabs keep the partial sums cheap
-            static const int sk256_on = tune_env("RF_SK256", 1);
-            if (sk256_on && d->act == RF_ACT_NONE) {
+            if (d->act == RF_ACT_NONE) {
                 const long long blocks = mt256 * nt * pick_splitk(d, p, mt256 * nt, bk);
                 if (blocks > mt256 * nt && blocks <= 4 * mt256 * nt && blocks >= 192 && blocks <= 256)
                     return n320 ? launch_cfg<T, TO, 4, 2, 2, 5, W8>(d, p, conv, st) : launch_cfg<T, TO, 4, 2, 2, 4, W8>(d, p, conv, st);
@@ -2366,10 +2031,6 @@ static int conv_gemm_impl(const rf_conv_gemm_desc* d, void* stream, int* plan) {
     p.ln_in = (const float*)d->ln_stats_in; p.ln_in_parts = d->ln_in_parts; p.ln_in_cols = d->ln_in_cols; p.ln_eps = d->ln_eps; p.ln_u = d->ln_u;
     RF_CHECK(!(p.ln_out || p.ln_in) || ((d->dtype == RF_BF16 || h16) && d->out_dtype == d->dtype && d->batch == 1 && !(p.ln_out && p.ln_in)),
              "rf_conv_gemm: LayerNorm folding is built for bf16 / fp16 GEMMs (batch 1, one role per launch)");
-    {
-        static const int dbg = tune_env("RF_GEMM_DBG", 0);
-        p.dbg = dbg;
-    }
     RF_CHECK(!(d->gn_part0 || d->gn_part1) || d->gn_rows > 0, "rf_conv_gemm: gn_part set but gn_rows = %d", d->gn_rows);
     {
         const uintptr_t oa = d->out_dtype == RF_F32 ? 16 : 8;
