@@ -407,6 +407,24 @@ int rf_maxpool3x3s2(const float* x, int B, int H, int W, int C, float* out, void
 int rf_add_relu(const float* a, const float* r, float* out, int64_t n, void* stream);
 int rf_scale_add_vec(const float* x, const float* s, const float* v, float* out, int B, int HW, int C, void* stream);
 int rf_parse_head(const float* logits, int B, int h, int w, int C, int ldl, int H, int W, const void* lut256_u8, void* out_u8, void* stream);
+/*
+ * Video paste-back (stage 3 of scripts/inference_swap_video.py:705-724): PIL's arithmetic, byte for byte (libImaging/Resample.c, Geometry.c).
+ *   rf_paste_crop_u8 : fp32 NCHW [B, 3, h, w] in [0, 1] (run_batch's result) -> u8 HWC [B, S, S, 3]: the reference's (255.f * x) truncation
+ *                      to u8, then Image.resize((S, S), BILINEAR): separable, horizontal pass first, u8 between the passes; per axis
+ *                      center = (i + .5) * in / out, taps [int(center - .5), int(center + 1.5)) clipped, triangle weights normalised to 1
+ *                      and made int(w * 2^22 + .5); out = clip((2^21 + sum k x) >> 22, 0, 255).  Upscale only (S >= h, w; else rc 1).
+ *   rf_paste_back_u8 : crops u8 [B, S, S, 3], coeffs fp64 [B, 8] (the inverse transforms of stage 1: frame -> crop), frames u8 [B, H, W, Cf]
+ *                      (frame b at frames + b * frame_stride bytes) -> out u8 [B, H, W, Co] (packed), Cf, Co in {3, 4}: Image.transform(
+ *                      (W, H), PERSPECTIVE, c, BILINEAR) of the alpha-255 crop alpha-composited over the frame.  Per pixel in fp64, PIL's
+ *                      operation order: d = c6 (x+.5) + c7 (y+.5) + 1, sx = (c0 (x+.5) + c1 (y+.5) + c2) / d, sy likewise; outside
+ *                      [0, S)^2 or not finite: the frame pixel (its alpha, or 255); inside: PIL's bilinear_filter32RGB (lerp along x on
+ *                      rows clamp(y0) and y0 + 1 if it exists, then along y), truncated, alpha 255.  One launch for the batch.
+ *                      out == frames is allowed when Cf == Co and frame_stride == H * W * Cf (every pixel is read before it is written);
+ *                      any other overlap of out with crops or frames is undefined.
+ */
+int rf_paste_crop_u8(const float* x, int B, int h, int w, int S, void* out_u8, void* stream);
+int rf_paste_back_u8(const void* crops_u8, int B, int S, const double* coeffs, const void* frames_u8, int H, int W, int Cf, int64_t frame_stride,
+                     void* out_u8, int Co, void* stream);
 /* elementwise y = silu(x) on fp32 (emb path, openaimodel.py:219) */
 int rf_silu_f32(const float* x, float* y, int64_t n, void* stream);
 

@@ -891,6 +891,35 @@ def resize_u8_linear(x_u8, out, name="resize_u8_linear"):
     return Launch(lib.rf_resize_u8_linear, (_p(x_u8), B, H, W_, Cc, x_u8.stride(0), out.shape[1], out.shape[2], _p(out)), (x_u8, out), name)
 
 
+def paste_crop_u8(result01, out, name="paste_crop_u8"):
+    """result01 fp32 [B, 3, h, w] in [0, 1] -> out uint8 [B, S, S, 3]: (255 * x).astype(uint8), then PIL's resize((S, S), BILINEAR) byte for
+    byte (rf_paste_crop_u8; upscale only)."""
+    lib = _lib.load()
+    _require_gpu(result01, out)
+    B, C3, h, w = result01.shape
+    S = out.shape[1]
+    assert C3 == 3 and result01.dtype == torch.float32 and result01.is_contiguous()
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == (B, S, S, 3)
+    return Launch(lib.rf_paste_crop_u8, (_p(result01), B, h, w, S, _p(out)), (result01, out), name)
+
+
+def paste_back_u8(crops_u8, coeffs, frames_u8, out, name="paste_back_u8"):
+    """PIL's PERSPECTIVE / BILINEAR warp of the crops uint8 [B, S, S, 3] by the inverse transforms coeffs fp64 [B, 8], alpha-composited over
+    frames uint8 [B, H, W, 3 | 4] (any frame stride) -> out uint8 [B, H, W, 3 | 4] (rf_paste_back_u8).  `out` may be `frames` itself when the
+    channel counts match and the frames are packed."""
+    lib = _lib.load()
+    _require_gpu(crops_u8, coeffs, frames_u8, out)
+    B, S = crops_u8.shape[0], crops_u8.shape[1]
+    _, H, W_, Cf = frames_u8.shape
+    assert crops_u8.dtype == torch.uint8 and crops_u8.is_contiguous() and crops_u8.shape == (B, S, S, 3)
+    assert coeffs.dtype == torch.float64 and coeffs.is_contiguous() and coeffs.shape == (B, 8)
+    assert frames_u8.dtype == torch.uint8 and frames_u8.shape[0] == B and frames_u8.stride(3) == 1 and frames_u8.stride(2) == Cf
+    assert frames_u8.stride(1) == W_ * Cf
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape[:3] == (B, H, W_)
+    return Launch(lib.rf_paste_back_u8, (_p(crops_u8), B, S, _p(coeffs), _p(frames_u8), H, W_, Cf, frames_u8.stride(0), _p(out), out.shape[3]),
+                  (crops_u8, coeffs, frames_u8, out), name)
+
+
 def label_mask(labels_u8, lut256, out, *, invert, name="label_mask"):
     lib = _lib.load()
     _require_gpu(labels_u8, lut256, out)

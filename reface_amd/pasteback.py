@@ -1,0 +1,154 @@
+"""Stage 3 of the video caller on the GPU: swapped crops warped back into their full frames (scripts/inference_swap_video.py:705-724 of the
+reference), with the reference's PIL arithmetic reproduced byte for byte by two HIP kernels (reface_amd/csrc/pasteback.hip):
+
+  crop  = Image.fromarray((255. * x_hwc).astype(uint8)).resize((1024, 1024), BILINEAR)        rf_paste_crop_u8
+  frame = Image.open(<Base_dir>/<video>/<int(sid)>.png)
+  c     = np.load(<Base_dir>/<video>_inv_transforms.npy, allow_pickle=True)[int(sid)]
+  crop.convert('RGBA') with alpha 255, transformed to frame.size (PERSPECTIVE, c, BILINEAR), alpha-composited over frame.convert('RGBA')
+                                                                                              rf_paste_back_u8
+The inverse transforms are stage 1's: ``alignment_coefficients(quad, 1024)`` of every frame's alignment quad (the reference's
+calc_alignment_coefficients(quad + 0.5, crop corners), :81-84).  Frame decoding and PNG encoding are host work on thread pools; the
+warp of a whole batch is one launch.
+"""
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import ops
+from .output import available_cpus
+
+CROP_SIZE = 1024          # the reference aligns to, and pastes back from, 1024^2 crops
+
+
+def alignment_coefficients(quad, size=CROP_SIZE):
+    """The 8 PIL PERSPECTIVE coefficients c that map a frame point (x, y) onto the crop: crop_x = (c0 x + c1 y + c2) / (c6 x + c7 y + 1),
+    crop_y = (c3 x + c4 y + c5) / (c6 x + c7 y + 1), such that the quad's corners (pixel centres: quad + 0.5) land on the crop's corners
+    (0, 0), (0, size), (size, size), (size, 0) in that order -- what stage 1 stores per frame in ``<video>_inv_transforms.npy``.
+    Each correspondence gives two linear equations in c (multiply out the denominator); four corners determine c exactly."""
+    src = np.asarray(quad, dtype=np.float64).reshape(4, 2) + 0.5
+    dst = np.array([[0, 0], [0, size], [size, size], [size, 0]], dtype=np.float64)
+    A = np.zeros((8, 8), dtype=np.float64)
+    for k, ((x, y), (u, v)) in enumerate(zip(src, dst)):
+        A[2 * k] = [x, y, 1, 0, 0, 0, -u * x, -u * y]
+        A[2 * k + 1] = [0, 0, 0, x, y, 1, -v * x, -v * y]
+    return np.linalg.solve(A, dst.reshape(8))
+
+
+def stage3_paths(base_dir, target_video):
+    """Where stage 1 of the reference leaves the full frames and their inverse transforms (:413, :496)."""
+    video = os.path.basename(target_video).split(".")[0]
+    return {"video_frames": os.path.join(base_dir, video), "inv_transforms": os.path.join(base_dir, video + "_inv_transforms.npy")}
+
+
+def load_inv_transforms(path):
+    """``<video>_inv_transforms.npy`` (a pickled object array of per-frame coefficient vectors, or a plain [N, 8] array) -> fp64 [N, 8]."""
+    a = np.load(path, allow_pickle=True)
+    out = np.stack([np.asarray(c, dtype=np.float64).reshape(8) for c in a]) if a.dtype == object else np.asarray(a, dtype=np.float64)
+    if out.ndim != 2 or out.shape[1] != 8:
+        raise ValueError(f"{path}: expected one 8-coefficient vector per frame, got shape {out.shape}")
+    return out
+
+
+def load_frame(frames_dir, sid):
+    """Frame ``<frames_dir>/<int(sid)>.png`` as uint8 HWC with 3 or 4 channels (other modes are converted to RGBA, as the reference's
+    ``orig_image.convert('RGBA')`` does)."""
+    from PIL import Image
+    im = Image.open(os.path.join(frames_dir, f"{int(sid)}.png"))
+    if im.mode not in ("RGB", "RGBA"):
+        im = im.convert("RGBA")
+    return np.asarray(im, dtype=np.uint8)
+
+
+class PasteBack:
+    """The device half of stage 3 for one video: ``prefetch(ids)`` starts decoding the frames of a batch on a thread pool; ``paste(result01,
+    ids)`` turns run_batch's fp32 [B, 3, h, w] result into the pasted frames (uint8 [H, W, channels] host arrays, one per id)."""
+
+    def __init__(self, frames_dir, inv_transforms, crop_size=CROP_SIZE, channels=4, threads=None):
+        self.frames_dir, self.S, self.channels = frames_dir, int(crop_size), int(channels)
+        self.coeffs = load_inv_transforms(inv_transforms) if isinstance(inv_transforms, str) else np.asarray(inv_transforms, dtype=np.float64)
+        self.pool = ThreadPoolExecutor(max_workers=threads or max(2, min(8, available_cpus() // 2)))
+
+    def prefetch(self, ids):
+        return [self.pool.submit(load_frame, self.frames_dir, sid) for sid in ids]
+
+    def paste(self, result01, ids, frames=None):
+        ids = list(ids)
+        if len(ids) != result01.shape[0]:
+            raise ValueError(f"{len(ids)} ids for a batch of {result01.shape[0]}")
+        idx = [int(s) for s in ids]
+        bad = [s for s, i in zip(ids, idx) if not 0 <= i < len(self.coeffs)]
+        if bad:
+            raise IndexError(f"frames {bad} have no inverse transform ({len(self.coeffs)} in the file)")
+        frames = [f.result() if hasattr(f, "result") else f for f in (frames if frames is not None else self.prefetch(ids))]
+        dev = result01.device
+        x = result01.float().contiguous()
+        crops = torch.empty((len(ids), self.S, self.S, 3), dtype=torch.uint8, device=dev)
+        ops.paste_crop_u8(x, crops)()
+        coeffs = torch.from_numpy(self.coeffs[idx]).to(dev)
+        out = [None] * len(ids)
+        groups = {}
+        for i, f in enumerate(frames):          # one launch per frame size (all frames of a video share one)
+            groups.setdefault(f.shape, []).append(i)
+        for shape, members in groups.items():
+            sel = torch.tensor(members, device=dev)
+            fr = torch.from_numpy(np.stack([frames[i] for i in members])).pin_memory().to(dev, non_blocking=True)
+            o = torch.empty(fr.shape[:3] + (self.channels,), dtype=torch.uint8, device=dev)
+            ops.paste_back_u8(crops.index_select(0, sel).contiguous(), coeffs.index_select(0, sel).contiguous(), fr, o)()
+            host = o.cpu().numpy()
+            for k, i in enumerate(members):
+                out[i] = host[k]
+        return out
+
+    def close(self):
+        self.pool.shutdown(wait=True)
+
+
+def paste_back(result01, ids, frames_dir, inv_transforms, outdir=None, crop_size=CROP_SIZE, channels=4):
+    """Paste run_batch's swapped crops (fp32 [B, 3, h, w] in [0, 1] on the device) into their frames ``<frames_dir>/<int(id)>.png`` with the
+    coefficients of ``inv_transforms`` (path of the .npy or an [N, 8] array).  Returns the pasted frames as uint8 HWC arrays (RGBA by default)
+    and, with ``outdir``, also writes them as ``<outdir>/<id>.png``."""
+    pb = PasteBack(frames_dir, inv_transforms, crop_size=crop_size, channels=channels)
+    try:
+        out = pb.paste(result01, ids)
+    finally:
+        pb.close()
+    if outdir is not None:
+        from PIL import Image
+        os.makedirs(outdir, exist_ok=True)
+        for sid, a in zip(ids, out):
+            Image.fromarray(a).save(os.path.join(outdir, f"{sid}.png"))
+    return out
+
+
+class PngWriter:
+    """PNG encodes of whole pasted frames off the launch thread (one job per file, like output.OutputWriter).  At most `depth` frames wait
+    (``submit`` then blocks on the oldest: a 1080p RGBA frame is 8 MB of host memory); ``close`` drains and raises the first error."""
+
+    def __init__(self, threads=None, depth=32):
+        self.pool = ThreadPoolExecutor(max_workers=threads or max(2, min(8, available_cpus() // 2)))
+        self.pending, self.depth, self.n = [], int(depth), 0
+
+    @staticmethod
+    def _save(path, arr):
+        from PIL import Image
+        Image.fromarray(arr).save(path)
+
+    def _reap(self, block):
+        while self.pending and (self.pending[0].done() or (block and len(self.pending) >= self.depth)):
+            self.pending.pop(0).result()
+            self.n += 1
+
+    def submit(self, path, arr):
+        self._reap(block=True)
+        self.pending.append(self.pool.submit(self._save, path, arr))
+
+    def close(self):
+        try:
+            while self.pending:
+                self.pending.pop(0).result()
+                self.n += 1
+        finally:
+            self.pool.shutdown(wait=True)
+        return self.n

@@ -6,8 +6,8 @@ The reference script has three stages.  Stage 1 (:430-500) decodes ``--target_vi
 ``--src_image`` (dlib / FFHQ alignment, keeping the inverse transforms) and writes face-parsing label maps (BiSeNet); stage 3
 (:690-760) warps every swapped crop back into its frame and encodes the mp4 with the original audio (moviepy).  Both are host-side
 I/O around models that are outside this build, so this CLI takes stage 1's on-disk product, in the reference's
-own layout, and leaves stage 3 to the reference (``--parse_masks`` writes the label maps below from the crops with the GPU face parser,
-reface_amd/parsing.py, when they are missing):
+own layout (``--parse_masks`` writes the label maps below from the crops with the GPU face parser, reface_amd/parsing.py, when they are
+missing):
 
   <Base_dir>/<video>cropped_face/<i>.png      aligned 1024^2 crops, one per frame           (:416, written at :489)
   <Base_dir>/<video>mask_frames/<i>.png       their face-parsing label maps                 (:417, :497)
@@ -18,6 +18,15 @@ Stage 2 is the test bench's batch body (reface_amd/pipeline.py) with the source 
 ``drop_last=True`` (:541: a trailing partial batch of frames is NOT swapped -- kept, it is the reference's behaviour); every
 swapped crop is written as the reference does before pasting, resized to 1024^2 (bilinear), to
 ``<outdir>/model_outputs/<frame id>.png`` (:690-691).
+
+Stage 3's paste-back runs with ``--paste_back`` (reface_amd/pasteback.py, :705-724): every swapped crop is enlarged to 1024^2 and warped into
+its full frame on the GPU with the reference's PIL arithmetic, byte for byte, and written as ``<outdir>/results/<frame id>.png`` (RGBA) by
+an encoder pool.  It reads two more products of stage 1, checked before anything is loaded:
+
+  <Base_dir>/<video>/<int(frame id)>.png      the full frames                               (:413, written at :475)
+  <Base_dir>/<video>_inv_transforms.npy       per frame, the 8 PERSPECTIVE coefficients     (:496)
+
+The mp4 + audio mux of stage 3 is not built (no video encoder in this build).
 """
 import argparse
 import os
@@ -80,6 +89,8 @@ def build_parser():
     p.add_argument("--num_workers", type=int, default=4)
     p.add_argument("--parse_masks", action="store_true", help="write missing face-parsing label maps from the existing crops with the GPU "
                    "face parser (--faceParsing_ckpt, 'none' = seeded weights; --seg12) before sampling")
+    p.add_argument("--paste_back", action="store_true", help="stage 3: paste every swapped crop back into its full frame on the GPU "
+                   "(<Base_dir>/<video>/<i>.png, <Base_dir>/<video>_inv_transforms.npy) and write <outdir>/results/<id>.png (RGBA)")
     return p
 
 
@@ -92,9 +103,37 @@ def prepared_paths(opt):
             "src": os.path.join(tmp, src + ".png"), "src_mask": os.path.join(tmp, os.path.basename(opt.src_image))}
 
 
+def pasteback_paths(opt):
+    """The reference's names for what stage 3 reads besides the crops: the full frames and their inverse transforms (:413, :496)."""
+    from reface_amd.pasteback import stage3_paths
+    return stage3_paths(opt.Base_dir, opt.target_video)
+
+
+def check_pasteback_inputs(opt, pp):
+    """Paths stage 3 needs that are missing: the frames directory and the .npy, then (when both exist) the frame of every crop that a
+    drop_last run swaps and its row of inverse transforms."""
+    sp = pasteback_paths(opt)
+    missing = [sp["video_frames"]] if not os.path.isdir(sp["video_frames"]) else []
+    missing += [sp["inv_transforms"]] if not os.path.isfile(sp["inv_transforms"]) else []
+    if missing or not os.path.isdir(pp["frames"]):
+        return missing
+    n = len(os.listdir(pp["frames"])) // max(1, opt.n_samples) * max(1, opt.n_samples)
+    missing += [p for p in (os.path.join(sp["video_frames"], f"{i}.png") for i in range(n)) if not os.path.isfile(p)]
+    from reface_amd.pasteback import load_inv_transforms
+    if len(load_inv_transforms(sp["inv_transforms"])) < n:
+        missing.append(f"{sp['inv_transforms']} (rows for frames 0..{n - 1})")
+    return missing
+
+
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     print(opt)
+    if opt.paste_back:
+        missing = check_pasteback_inputs(opt, prepared_paths(opt))
+        if missing:
+            raise SystemExit("inference_swap_video: --paste_back needs the full frames and the inverse alignment transforms that stage 1 of the "
+                             "reference writes (inference_swap_video.py:475, :496); missing:\n  " + "\n  ".join(missing[:8]) +
+                             (f"\n  ... and {len(missing) - 8} more" if len(missing) > 8 else ""))
     torch.manual_seed(opt.seed)
     np.random.seed(opt.seed)
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -138,7 +177,7 @@ def main(argv=None):
     runner = SwapRunner(model, sampler, opt)
     model_out = os.path.join(opt.outdir, "model_outputs")
     os.makedirs(model_out, exist_ok=True)
-    os.makedirs(os.path.join(opt.outdir, "results"), exist_ok=True)      # stage 3 of the reference fills it (pasted frames)
+    os.makedirs(os.path.join(opt.outdir, "results"), exist_ok=True)      # stage 3 fills it (pasted frames: --paste_back)
     test_args = dict(config.data.params.test.params)
     ref1 = load_source_reference(pp["src"], pp["src_mask"], test_args["preserve_mask_src_FFHQ"]).to(device)
     ds = VideoDataset(data_path=pp["frames"], mask_path=pp["masks"], **test_args)
@@ -147,8 +186,14 @@ def main(argv=None):
     if opt.fixed_code:      # ONE latent, repeated over the batch (:549-552) -- not one per sample as in the selected-swap caller
         start_code = torch.randn([opt.C, opt.H // opt.f, opt.W // opt.f], device=device).unsqueeze(0).repeat(opt.n_samples, 1, 1, 1)
     n_done = 0
+    paster = writer = None
+    if opt.paste_back and not opt.skip_save:
+        from reface_amd.pasteback import PasteBack, PngWriter
+        sp = pasteback_paths(opt)
+        paster, writer = PasteBack(sp["video_frames"], sp["inv_transforms"]), PngWriter()
     with torch.no_grad(), model.ema_scope():
         for test_batch, prior, kw, ids in loader:
+            frames = paster.prefetch(ids) if paster is not None else None          # decoded on the pool while the batch samples
             if opt.Start_from_target:
                 start_code = runner.start_from_target(test_batch)        # `use_prior = False` (:555)
             kw = {n: kw[n].to(device, non_blocking=True) for n in kw}
@@ -160,9 +205,18 @@ def main(argv=None):
             res = x_img.cpu().numpy()
             for i, sid in enumerate(ids):
                 Image.fromarray(O.to_u8_hwc(res[i])).resize((1024, 1024), Image.BILINEAR).save(os.path.join(model_out, sid + ".png"))
+            if paster is not None:          # stage 3 (:705-724): the crops enlarged and warped into their frames on the device, PNGs encoded off this thread
+                for sid, frame in zip(ids, paster.paste(x_img, ids, frames)):
+                    writer.submit(os.path.join(opt.outdir, "results", sid + ".png"), frame)
     torch.cuda.synchronize()
-    print(f"Swapped crops of {n_done} frames are in {model_out}; the reference's stage 3 (paste back with the inverse alignment of every frame, "
-          f"mp4 + audio) takes them from there.")
+    if paster is not None:
+        paster.close()
+        n_pasted = writer.close()
+        print(f"Swapped crops of {n_done} frames are in {model_out}; {n_pasted} pasted frames are in {os.path.join(opt.outdir, 'results')} "
+              f"(the mp4 + audio mux of the reference's stage 3 is not built).")
+    else:
+        print(f"Swapped crops of {n_done} frames are in {model_out}; the reference's stage 3 (paste back with the inverse alignment of every frame, "
+              f"mp4 + audio) takes them from there (--paste_back pastes them back on the GPU).")
     return n_done
 
 
