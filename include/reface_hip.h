@@ -425,6 +425,27 @@ int rf_parse_head(const float* logits, int B, int h, int w, int C, int ldl, int 
 int rf_paste_crop_u8(const float* x, int B, int h, int w, int S, void* out_u8, void* stream);
 int rf_paste_back_u8(const void* crops_u8, int B, int S, const double* coeffs, const void* frames_u8, int H, int W, int Cf, int64_t frame_stride,
                      void* out_u8, int Co, void* stream);
+/*
+ * Face alignment (stage 1 of the swap callers, src/utils/alignmengt.py:crop_image): PIL's arithmetic, byte for byte (libImaging/Geometry.c,
+ * Resample.c) -- the mirror image of the paste-back above.
+ *   rf_align_quad_u8 : frames u8 [B, H, W, Cf] (frame b at frames + b * frame_stride bytes, Cf in {3, 4}: only R, G, B are read), coeffs fp64
+ *                      [B, 8] -> out u8 [B, S, S, 3]: Image.transform((S, S), QUAD, quad, BILINEAR), the coefficients being those PIL makes
+ *                      of the quad (reface_amd.align.quad_coefficients).  Per output pixel in fp64, PIL's operation order: xin = x + .5,
+ *                      yin = y + .5, xs = a0 + a1 xin + a2 yin + a3 xin yin, ys = a4 + a5 xin + a6 yin + a7 xin yin; outside the source
+ *                      (tested before the -.5 shift) or not finite: 0; inside: PIL's bilinear_filter32RGB, truncated.  `windows` (int32
+ *                      [B, 4] on the device, or NULL) gives per frame the sub-rectangle (ox, oy, w, h) that is the source image -- the
+ *                      reference's img.crop(...) before the transform, without a copy; a window not inside the frame gives zeros.
+ *                      One launch for the batch.  out must not overlap the frames.
+ *   rf_resample_u8   : x u8 [B, H, W, C] -> out u8 [B, h, w, C], C in {3, 4}: PIL's two-pass integer resampler (horizontal pass into tmp u8
+ *                      [B, H, w, C], then vertical) with the host's tap tables (reface_amd.align.resample_taps, PIL's precompute_coeffs +
+ *                      normalize_coeffs_8bpc): per axis, bounds int32 [n_out, 2] = (first input index, tap count) and taps int32
+ *                      [n_out, ksize], all on the device; each pass is clip8(((1 << 21) + sum k p) >> 22).  Tap windows are clipped to
+ *                      the axis.  x, tmp and out are three distinct buffers.
+ */
+int rf_align_quad_u8(const void* frames_u8, int B, int H, int W, int Cf, int64_t frame_stride, const double* coeffs, const int* windows, int S,
+                     void* out_u8, void* stream);
+int rf_resample_u8(const void* x_u8, int B, int H, int W, int C, const int* xbounds, const int* xk, int xksize, const int* ybounds, const int* yk,
+                   int yksize, void* tmp_u8, void* out_u8, int h, int w, void* stream);
 /* elementwise y = silu(x) on fp32 (emb path, openaimodel.py:219) */
 int rf_silu_f32(const float* x, float* y, int64_t n, void* stream);
 

@@ -3,7 +3,7 @@
 // Both are byte-level and memory-bound; each thread handles 4 consecutive output pixels so that a group's bytes leave in 32-bit words.
 // The arithmetic is PIL's own (libImaging/Resample.c, Geometry.c), operation for operation; the unit builds with -ffp-contract=off, so none
 // of the fp64 coordinate / lerp expressions below is contracted to an FMA (the only v_fma_f64 in the ISA are inside the two IEEE divisions).
-#include "common.h"
+#include "pil_u8.h"
 
 namespace rf {
 
@@ -33,8 +33,6 @@ __device__ __forceinline__ void pil_taps(int i, int n_in, int n_out, int& lo, in
 #pragma unroll
     for (int x = 0; x < 2; ++x) k[x] = x < n ? (int)(0.5 + (ww != 0.0 ? w[x] / ww : w[x]) * (double)(1 << 22)) : 0;
 }
-
-__device__ __forceinline__ int pil_clip8(int s) { return min(max(s >> 22, 0), 255); }
 
 // (255.f * x).astype(uint8) of the reference: fp32 product, truncation toward zero, low byte
 __device__ __forceinline__ int u8_of(float v) { return (int)(255.0f * v) & 0xff; }
@@ -134,25 +132,7 @@ __global__ void paste_back_kernel(const uint8_t* __restrict__ crops, int S, cons
             any_out = true;
             continue;
         }
-        const double u = sx - 0.5, v = sy - 0.5;
-        const double fx = floor(u), fy = floor(v);
-        const int x0 = (int)fx, y0 = (int)fy;
-        const double dx = u - fx, dy = v - fy;
-        const int cx0 = min(max(x0, 0), S - 1), cx1 = min(max(x0 + 1, 0), S - 1), cy0 = min(max(y0, 0), S - 1);
-        const bool row2 = y0 + 1 >= 0 && y0 + 1 < S;
-        const uint8_t* r0 = crop + (long long)cy0 * S * 3;
-        const uint8_t* r1 = row2 ? crop + (long long)(y0 + 1) * S * 3 : r0;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const double a0 = (double)r0[cx0 * 3 + ch], b0 = (double)r0[cx1 * 3 + ch];
-            const double v1 = a0 + (b0 - a0) * dx;
-            double v2 = v1;
-            if (row2) {
-                const double a1 = (double)r1[cx0 * 3 + ch], b1 = (double)r1[cx1 * 3 + ch];
-                v2 = a1 + (b1 - a1) * dx;
-            }
-            px[q][ch] = (uint8_t)(int)(v1 + (v2 - v1) * dy);
-        }
+        pil_bilinear_rgb<3>(crop, S, S, (long long)S * 3, sx, sy, px[q]);
     }
     if (any_out) {                // the frame's bytes of this group: Cf words when aligned and whole, else per byte
         uint8_t fb[4 * Cf];
@@ -176,20 +156,7 @@ __global__ void paste_back_kernel(const uint8_t* __restrict__ crops, int S, cons
 #pragma unroll
                 for (int ch = 0; ch < Cf; ++ch) px[q][ch] = fb[q * Cf + ch];
     }
-    if (nq == 4 && ((uintptr_t)o & 3) == 0) {
-        uint32_t* ow = (uint32_t*)o;
-#pragma unroll
-        for (int j = 0; j < Co; ++j) {
-            uint32_t word = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) word |= (uint32_t)px[(4 * j + k) / Co][(4 * j + k) % Co] << (8 * k);
-            ow[j] = word;
-        }
-    } else {
-        for (int q = 0; q < nq; ++q)
-#pragma unroll
-            for (int ch = 0; ch < Co; ++ch) o[q * Co + ch] = px[q][ch];
-    }
+    store_px4<Co>(o, px, nq);
 }
 
 }  // namespace rf

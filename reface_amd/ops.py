@@ -920,6 +920,39 @@ def paste_back_u8(crops_u8, coeffs, frames_u8, out, name="paste_back_u8"):
                   (crops_u8, coeffs, frames_u8, out), name)
 
 
+def align_quad_u8(frames_u8, coeffs, out, windows=None, name="align_quad_u8"):
+    """PIL's Image.transform((S, S), QUAD, quad, BILINEAR) of frames uint8 [B, H, W, 3 | 4] (any frame stride; R, G, B are read) by the QUAD
+    coefficients coeffs fp64 [B, 8] -> out uint8 [B, S, S, 3], byte for byte (rf_align_quad_u8).  `windows` int32 [B, 4] = (ox, oy, w, h)
+    makes a sub-rectangle of every frame the source image (PIL's crop before the transform, without the copy)."""
+    lib = _lib.load()
+    _require_gpu(frames_u8, coeffs, out, windows)
+    B, H, W_, Cf = frames_u8.shape
+    S = out.shape[1]
+    assert frames_u8.dtype == torch.uint8 and frames_u8.stride(3) == 1 and frames_u8.stride(2) == Cf and frames_u8.stride(1) == W_ * Cf
+    assert coeffs.dtype == torch.float64 and coeffs.is_contiguous() and coeffs.shape == (B, 8)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == (B, S, S, 3)
+    assert windows is None or (windows.dtype == torch.int32 and windows.is_contiguous() and windows.shape == (B, 4))
+    return Launch(lib.rf_align_quad_u8, (_p(frames_u8), B, H, W_, Cf, frames_u8.stride(0) if B > 1 else H * W_ * Cf, _p(coeffs), _p(windows), S, _p(out)),
+                  (frames_u8, coeffs, windows, out), name)
+
+
+def resample_u8(x_u8, xtaps, ytaps, tmp, out, name="resample_u8"):
+    """PIL's two-pass integer resampler (Image.resize with a convolution filter) of x uint8 [B, H, W, 3 | 4] -> out uint8 [B, h, w, C] through
+    tmp uint8 [B, H, w, C], byte for byte (rf_resample_u8).  xtaps / ytaps = (bounds int32 [n_out, 2], taps int32 [n_out, ksize]) on the
+    device: reface_amd.align.resample_taps of each axis."""
+    lib = _lib.load()
+    (xb, xk), (yb, yk) = xtaps, ytaps
+    _require_gpu(x_u8, xb, xk, yb, yk, tmp, out)
+    B, H, W_, Cc = x_u8.shape
+    h, w = out.shape[1], out.shape[2]
+    assert x_u8.dtype == tmp.dtype == out.dtype == torch.uint8 and x_u8.is_contiguous() and tmp.is_contiguous() and out.is_contiguous()
+    assert tmp.shape == (B, H, w, Cc) and out.shape == (B, h, w, Cc)
+    for b, k, n in ((xb, xk, w), (yb, yk, h)):
+        assert b.dtype == k.dtype == torch.int32 and b.is_contiguous() and k.is_contiguous() and b.shape == (n, 2) and k.ndim == 2 and k.shape[0] == n
+    return Launch(lib.rf_resample_u8, (_p(x_u8), B, H, W_, Cc, _p(xb), _p(xk), xk.shape[1], _p(yb), _p(yk), yk.shape[1], _p(tmp), _p(out), h, w),
+                  (x_u8, xb, xk, yb, yk, tmp, out), name)
+
+
 def label_mask(labels_u8, lut256, out, *, invert, name="label_mask"):
     lib = _lib.load()
     _require_gpu(labels_u8, lut256, out)

@@ -4,8 +4,12 @@
 
 The reference script has two stages.  Stage 1 (:440-512) aligns and crops the raw ``--target_folder`` / ``--src_folder`` images
 (dlib / FFHQ alignment) and writes face-parsing label maps (BiSeNet, ``--faceParsing_ckpt``) into ``<Base_dir>/{target_cropped,
-mask_frames,source_cropped,source_mask}``.  The alignment is outside the scope of this build, so this CLI expects
-the crops to exist (the reference's stage 1, or any tool writing ``<i>.png`` crops + label maps, produces them); ``--parse_masks`` writes
+mask_frames,source_cropped,source_mask}``.  Without ``--align`` this CLI expects
+the crops to exist (the reference's stage 1, or any tool writing ``<i>.png`` crops + label maps, produces them); ``--align`` writes
+``target_cropped/<i>.png`` and ``source_cropped/<i>.png`` from the images of ``--target_folder`` / ``--src_folder`` (sorted by name) on the
+GPU (reface_amd/align.py: the FFHQ quad from 68 landmarks, PIL's resampling byte for byte), the landmarks coming from ``--landmarks`` /
+``--src_landmarks`` (.npy, [N, 68, 2] in that order) or from dlib where it is installed -- landmark detection is not built; an image
+without a face (non-finite landmarks) is skipped and the numbering closes up, as in the reference.  ``--parse_masks`` writes
 missing label maps from the crops with the GPU face parser (reface_amd/parsing.py).  Stage 2 -- the
 sampling loop -- is the same batch body as the test bench (reface_amd/pipeline.py) with ONE source face repeated over the batch
 (:649-653); outputs as the reference writes them: ``<outdir>/results/<s>/<id>.png``, ``<outdir>/grid/<s>/grid-<id>.png``,
@@ -72,15 +76,50 @@ def build_parser():
     p.add_argument("--num_workers", type=int, default=4)
     p.add_argument("--parse_masks", action="store_true", help="write missing face-parsing label maps from the existing crops with the GPU "
                    "face parser (--faceParsing_ckpt, 'none' = seeded weights; --seg12) before sampling")
+    p.add_argument("--align", action="store_true", help="stage 1: align the images of --target_folder / --src_folder on the GPU from their 68 "
+                   "landmarks into <Base_dir>/target_cropped and <Base_dir>/source_cropped")
+    p.add_argument("--landmarks", type=str, default=None, help="--align: .npy of the target images' landmarks [N, 68, 2] (sorted file order; "
+                   "non-finite row = no face); without it they come from dlib")
+    p.add_argument("--src_landmarks", type=str, default=None, help="--align: the same for the images of --src_folder")
     return p
+
+
+def check_align_inputs(opt):
+    """What --align reads, checked without touching the GPU: per folder, (paths of the images with a face, their landmarks, output folder)."""
+    from reface_amd import align as A
+    jobs, problems = [], []
+    for folder, arg, flag, out in ((opt.target_folder, opt.landmarks, "--landmarks", "target_cropped"),
+                                   (opt.src_folder, opt.src_landmarks, "--src_landmarks", "source_cropped")):
+        files = sorted(os.path.join(folder, f) for f in os.listdir(folder)) if os.path.isdir(folder) else []
+        if not files:
+            problems.append(f"{folder} (a folder of images)")
+            continue
+        try:
+            lm = A.landmarks_for(files, arg, f"the images of {folder} ({flag})")
+        except ValueError as e:
+            problems.append(str(e))
+            continue
+        keep = [i for i in range(len(files)) if np.isfinite(lm[i]).all()]
+        if not keep:
+            problems.append(f"{folder}: no image has a face (all landmarks are non-finite)")
+        jobs.append(([files[i] for i in keep], lm[keep], os.path.join(opt.Base_dir, out)))
+    if problems:
+        raise SystemExit("inference_swap_selected: --align needs the image folders and 68 landmarks per image; problems:\n  " + "\n  ".join(problems))
+    return jobs
 
 
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     print(opt)
+    align_jobs = check_align_inputs(opt) if opt.align else []
     torch.manual_seed(opt.seed)
     np.random.seed(opt.seed)
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
+    for files, lm, out in align_jobs:          # stage 1's alignment on the GPU
+        from reface_amd.align import align_to_disk
+        os.makedirs(out, exist_ok=True)
+        align_to_disk(files, lm, [os.path.join(out, f"{i}.png") for i in range(len(files))], batch=max(1, opt.n_samples))
+        print(f"inference_swap_selected: {len(files)} aligned crops written to {out}")
     base = opt.Base_dir
     tc, tm, sc, sm = (os.path.join(base, d) for d in ("target_cropped", "mask_frames", "source_cropped", "source_mask"))
     if opt.parse_masks:             # stage 1's parsing half on the GPU: label maps of the crops whose map folder is missing or empty

@@ -26,6 +26,14 @@ an encoder pool.  It reads two more products of stage 1, checked before anything
   <Base_dir>/<video>/<int(frame id)>.png      the full frames                               (:413, written at :475)
   <Base_dir>/<video>_inv_transforms.npy       per frame, the 8 PERSPECTIVE coefficients     (:496)
 
+Stage 1's alignment runs with ``--align`` (reface_amd/align.py, src/utils/alignmengt.py of the reference): from 68 landmarks per frame, the
+FFHQ quad, PIL's LANCZOS shrink and QUAD / BILINEAR resampling on the GPU, byte for byte, before any model loads.  It reads the full frames
+``<Base_dir>/<video>/<i>.png`` (i = 0 .. N-1; there is no video decoder in this build, so the frames arrive as PNGs) and ``--src_image``,
+and writes ``<Base_dir>/<video>cropped_face/<i>.png``, ``<Base_dir>/<video>_inv_transforms.npy`` and ``<outdir>/temp_results/<src>.png``.
+Landmarks come from ``--landmarks FILE.npy`` ([N, 68, 2]) and ``--src_landmarks FILE.npy`` ([68, 2]), or from dlib where it is installed
+(landmark detection is not built).  A frame whose landmarks are not finite ("no face") repeats the previous frame's crop and transform, as
+the reference's ``except`` branch does.  ``--align --parse_masks --paste_back`` together run raw frames to pasted frames in one command.
+
 The mp4 + audio mux of stage 3 is not built (no video encoder in this build).
 """
 import argparse
@@ -91,6 +99,11 @@ def build_parser():
                    "face parser (--faceParsing_ckpt, 'none' = seeded weights; --seg12) before sampling")
     p.add_argument("--paste_back", action="store_true", help="stage 3: paste every swapped crop back into its full frame on the GPU "
                    "(<Base_dir>/<video>/<i>.png, <Base_dir>/<video>_inv_transforms.npy) and write <outdir>/results/<id>.png (RGBA)")
+    p.add_argument("--align", action="store_true", help="stage 1: align the full frames <Base_dir>/<video>/<i>.png and --src_image on the GPU from "
+                   "their 68 landmarks; writes <video>cropped_face/, <video>_inv_transforms.npy and temp_results/<src>.png")
+    p.add_argument("--landmarks", type=str, default=None, help="--align: .npy of the frames' landmarks [N, 68, 2] (non-finite row = no face); "
+                   "without it they come from dlib")
+    p.add_argument("--src_landmarks", type=str, default=None, help="--align: .npy of --src_image's landmarks [68, 2]; without it they come from dlib")
     return p
 
 
@@ -125,9 +138,55 @@ def check_pasteback_inputs(opt, pp):
     return missing
 
 
+def check_align_inputs(opt):
+    """What --align reads, checked without touching the GPU: (frame paths, their landmarks [N, 68, 2], the source's landmarks [1, 68, 2]).
+    Exits naming what is missing or malformed."""
+    from reface_amd import align as A
+    frames_dir = pasteback_paths(opt)["video_frames"]
+    problems = []
+    n = len([f for f in os.listdir(frames_dir) if f.endswith(".png")]) if os.path.isdir(frames_dir) else 0
+    if n == 0:
+        problems.append(f"{frames_dir} (the full frames <i>.png, i = 0 .. N-1)")
+    paths = [os.path.join(frames_dir, f"{i}.png") for i in range(n)]
+    problems += [p for p in paths if not os.path.isfile(p)]
+    if not os.path.isfile(opt.src_image):
+        problems.append(f"{opt.src_image} (--src_image)")
+    lm = src_lm = None
+    if not problems:
+        for what, files, arg in (("the frames (--landmarks)", paths, opt.landmarks), ("--src_image (--src_landmarks)", [opt.src_image], opt.src_landmarks)):
+            try:
+                got = A.landmarks_for(files, arg, what)
+                A.fill_missing(got)
+            except ValueError as e:
+                problems.append(f"{what}: {e}")
+                continue
+            lm, src_lm = (got, src_lm) if files is paths else (lm, got)
+    if problems:
+        raise SystemExit("inference_swap_video: --align needs the full frames, the source image and 68 landmarks for each; problems:\n  " +
+                         "\n  ".join(problems[:8]) + (f"\n  ... and {len(problems) - 8} more" if len(problems) > 8 else ""))
+    return paths, lm, src_lm
+
+
+def run_align(opt, paths, lm, src_lm):
+    """Stage 1's alignment on the GPU: the crops of every frame, their inverse transforms and the aligned source."""
+    from reface_amd.align import align_to_disk
+    pp = prepared_paths(opt)
+    os.makedirs(pp["frames"], exist_ok=True)
+    os.makedirs(os.path.dirname(pp["src"]), exist_ok=True)
+    align_to_disk([opt.src_image], src_lm, [pp["src"]])
+    inv = align_to_disk(paths, lm, [os.path.join(pp["frames"], f"{i}.png") for i in range(len(paths))], batch=max(1, opt.n_samples))
+    np.save(pasteback_paths(opt)["inv_transforms"], inv)
+    print(f"inference_swap_video: {len(paths)} frames aligned into {pp['frames']} ({int((~np.isfinite(lm).all(axis=(1, 2))).sum())} without a face "
+          f"repeat the previous one); inverse transforms in {pasteback_paths(opt)['inv_transforms']}")
+
+
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     print(opt)
+    aligned = check_align_inputs(opt) if opt.align else None
+    if aligned is not None:
+        torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
+        run_align(opt, *aligned)
     if opt.paste_back:
         missing = check_pasteback_inputs(opt, prepared_paths(opt))
         if missing:

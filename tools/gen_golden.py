@@ -8,7 +8,7 @@ as small ``.npz`` fixtures under tests/golden/.  Only DATA is stored (tensors + 
 needed to regenerate the weights); no reference source is copied.
 
 Usage:  python tools/gen_golden.py [group ...]     (groups: schedule unet_ops unet_small unet_full
-                                                    ddim vae arcface clip e2e bisenet)
+                                                    ddim vae arcface clip e2e bisenet align)
 """
 import os
 import sys
@@ -580,9 +580,71 @@ def gen_bisenet():
          seed=91, small_seed=92, big_seed=93)
 
 
+def seeded_frame(h, w, c, seed, block=4):
+    """Deterministic uint8 frame [h, w, c]: seeded noise in block x block tiles (tests/test_align_cpu.py regenerates it the same way); a
+    fourth channel is alpha 255 (a decoded video frame is opaque)."""
+    a = seeded_u8(((h + block - 1) // block, (w + block - 1) // block, 3), seed).numpy()
+    a = np.repeat(np.repeat(a, block, axis=0), block, axis=1)[:h, :w]
+    return np.concatenate([a, np.full((h, w, 1), 255, np.uint8)], axis=2) if c == 4 else a
+
+
+def synthetic_landmarks(centre, eye_dist, degrees, seed):
+    """68 landmarks of a made-up face: eye centres eye_dist apart around `centre`, the mouth 0.9 eye_dist below them, turned by `degrees`;
+    every point jittered by a seeded fraction of a pixel (non-integer coordinates)."""
+    rng = np.random.default_rng(seed)
+    t = np.deg2rad(degrees)
+    R = np.array([[np.cos(t), -np.sin(t)], [np.sin(t), np.cos(t)]])
+    lm = rng.uniform(-1.0, 1.0, (68, 2)) * eye_dist
+    lm[36:42] = np.array([-0.5, 0.0]) * eye_dist + rng.uniform(-0.12, 0.12, (6, 2)) * eye_dist
+    lm[42:48] = np.array([0.5, 0.0]) * eye_dist + rng.uniform(-0.12, 0.12, (6, 2)) * eye_dist
+    lm[48:60] = np.array([0.0, 0.9]) * eye_dist + rng.uniform(-0.3, 0.3, (12, 2)) * eye_dist
+    lm[48], lm[54] = np.array([-0.35, 0.9]) * eye_dist, np.array([0.37, 0.92]) * eye_dist
+    return lm @ R.T + np.asarray(centre, dtype=np.float64)
+
+
+# (name, W, H, channels, frame seed, face centre, eye distance, rotation in degrees): a quad well inside its frame, one hanging over the
+# top and left edges, an RGBA frame, and a face large enough for crop_image's LANCZOS shrink at both output sizes (6 at 128, 3 at 256)
+ALIGN_CASES = [("inside", 640, 480, 3, 201, (330.0, 215.0), 50.0, 12.0), ("over_edges", 700, 500, 3, 202, (120.0, 95.0), 90.0, -9.0),
+               ("rgba", 640, 480, 4, 203, (300.0, 230.0), 60.0, -20.0), ("shrink", 2401, 1799, 3, 204, (1200.0, 800.0), 300.0, 7.0)]
+ALIGN_SIZES = (128, 256)
+
+
+def gen_align():
+    """Face alignment (src/utils/alignmengt.py): c, x, y and the quad of compute_transform, crop_image's crops at two output sizes and
+    calc_alignment_coefficients' inverse transforms, from the reference's own functions on synthetic frames and landmarks.  The packages
+    that file imports and this container lacks (skimage, cv2; dlib is stubbed by ref_shims) carry no arithmetic used here."""
+    import importlib
+    import PIL.Image
+    for name in ("skimage", "skimage.io", "cv2", "tqdm"):
+        try:
+            importlib.import_module(name)
+        except ImportError:
+            m = ref_shims._mod(name)
+            if name == "tqdm":
+                m.tqdm = lambda it, **k: it
+    if not hasattr(PIL.Image, "ANTIALIAS"):
+        PIL.Image.ANTIALIAS = PIL.Image.LANCZOS          # the name Pillow 10 dropped
+    from src.utils import alignmengt as A
+    out = {"names": np.array([c[0] for c in ALIGN_CASES]), "sizes": np.array(ALIGN_SIZES),
+           "frames": np.array([c[1:5] for c in ALIGN_CASES], dtype=np.int64)}          # W, H, channels, seed
+    for name, W, H, C, seed, centre, eye, deg in ALIGN_CASES:
+        lm = synthetic_landmarks(centre, eye, deg, seed + 100)
+        A.get_landmark = lambda *a, **k: lm
+        c, x, y = A.compute_transform("unused", None)
+        quad = np.stack([c - x - y, c - x + y, c + x + y, c + x - y])
+        frame = PIL.Image.fromarray(seeded_frame(H, W, C, seed))
+        out.update({f"{name}_landmarks": lm, f"{name}_c": c, f"{name}_x": x, f"{name}_y": y, f"{name}_quad": quad})
+        for S in ALIGN_SIZES:
+            crop = A.crop_image(frame, S, quad.copy()).convert("RGB")
+            assert crop.size == (S, S)
+            out[f"{name}_crop{S}"] = np.asarray(crop)
+            out[f"{name}_inv{S}"] = A.calc_alignment_coefficients(quad + 0.5, [[0, 0], [0, S], [S, S], [S, 0]])
+    save("align", **out)
+
+
 GROUPS = dict(ddim_full=gen_ddim_full, unet_keys=gen_unet_keys, plms=gen_plms, schedule=gen_schedule, unet_ops=gen_unet_ops, unet_small=gen_unet_small, unet_full=gen_unet_full,
               ddim=gen_ddim, vae=gen_vae, arcface=gen_arcface, clip=gen_clip, e2e=gen_e2e,
-              bisenet=gen_bisenet)
+              bisenet=gen_bisenet, align=gen_align)
 
 if __name__ == "__main__":
     sel = sys.argv[1:] or [g for g in GROUPS if g != "ddim_full"]          # (ddim_full: 20 minutes; ask for it by name)
