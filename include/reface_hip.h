@@ -127,6 +127,15 @@ typedef struct rf_conv_gemm_desc {
     /* W + s * w_sample_stride (elements); 0 = one W for all rows.  rows_per_sample must be a multiple of the tile rows (rf_conv_gemm_plan2's BM). */
     /* What rf_groupnorm_fold_linear writes: a GroupNorm folded into the weights of the Linear / 1x1 conv behind it. */
     int64_t w_sample_stride;
+    /* Centre-tap tail source (dtype RF_BF16 / RF_F16, a k x k window of ONE source on the direct-to-LDS loop): with srcx != NULL the contraction */
+    /* runs on behind the window, K = KH*KW*C0 + Cx, over the Cx channels of srcx at the OUTPUT pixel -- A[m, KH*KW*C0 + c] = srcx[pixel(m)][c] */
+    /* -- against the Cx tail columns of every W row (behind the window's columns, which keep their korder).  stride 1, no ups, Hin = Hout, */
+    /* Win = Wout, C1 = 0, batch 1, no fp8 / split-bf16 operands, C0 and Cx multiples of the K tile (64).  What it replaces: the 1x1 */
+    /* skip_connection of a ResBlock whose channel count changes (openaimodel.py:241, 262) as a launch of its own, the write of its output and */
+    /* the re-read of that tensor as the residual of out_layers.3 -- one contraction over [im2col(h) | x] with the two biases summed by the caller. */
+    const void* srcx;
+    int32_t Cx;
+    int32_t ldx;
 } rf_conv_gemm_desc;
 
 int rf_conv_gemm(const rf_conv_gemm_desc* d, void* stream);

@@ -41,6 +41,7 @@ class ConvGemmDesc(C.Structure):
         ("ln_stats_out", C.c_void_p), ("ln_out_parts", C.c_int32),
         ("ln_stats_in", C.c_void_p), ("ln_in_parts", C.c_int32), ("ln_in_cols", C.c_int32), ("ln_eps", C.c_float), ("ln_u", C.c_void_p),
         ("w_sample_stride", C.c_int64),
+        ("srcx", C.c_void_p), ("Cx", C.c_int32), ("ldx", C.c_int32),
     ]
 
 

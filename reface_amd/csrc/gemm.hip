@@ -83,6 +83,10 @@ struct GemmParams {
                      // (A lo, W hi); W rows hold them in that order, the A lo plane lies lo_off bytes behind the hi plane of the same pixel
     int lo_off;
     long long w_ps;  // per-sample weights (rf_conv_gemm_desc.w_sample_stride, elements): the rows of sample s multiply W + s * w_ps; 0 = one W
+    // centre-tap tail source (rf_conv_gemm_desc.srcx): K tiles [xt0, K / BK) read the channels of srcx at the output pixel; xt0 = 0x7fffffff: no tail
+    const void* srcx;
+    int ldx, xt0;
+    unsigned x_bytes;
 };
 
 // 8 fp8 (e4m3fn) weights -> 8 bf16, times the row's power-of-two scale: v_cvt_scalef32_pk_bf16_fp8, one instruction per pair (exact:
@@ -386,7 +390,12 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
         // Host guarantees (launch_typed): one source, K % BK == 0 and, for convs, Ctot % BK == 0 with tap-major K -- so a K tile
         // lies inside ONE filter tap and all of its addresses are  per-lane offset (fixed within a tap) + uniform K offset
         // (SGPR soffset).  Out-of-range rows / padding taps carry an out-of-range voffset: the buffer range check returns zeros.
-        const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)src0, 0, p.a_bytes, 0x00020000);
+        // XT: a centre-tap tail source may follow the window's K tiles (GemmParams.srcx): from tile xt0 on the A pieces come from srcx -- its own
+        // buffer resource, per-lane offsets of the output pixel (computed once, on entering the tail), the usual SGPR K offset per tile.  All of
+        // the tail's state is wave-uniform; launches without a tail (xt0 beyond every tile) run the loop as it was.
+        constexpr bool XT = CONV && is16<T>::value && !W8;
+        const int xt0 = XT ? p.xt0 : 0x7fffffff;
+        __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)src0, 0, p.a_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)Wp, 0, p.w_bytes, 0x00020000);
         constexpr int OOB = 0x7fffffff;
         constexpr int NP = AV + BV;
@@ -450,17 +459,19 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
             }
         }
         // HX: A-piece offsets of filter row dy (3x3, stride 1, pad 1: input row oy + dy - 1, input column xc - 1), once per dy
-        auto set_grp = [&](int dy) {
+        // (ld: pixel pitch of the source the pieces read -- src0, or the tail source, whose row-extended tile is that of filter row 1)
+        auto set_grp = [&](int dy, int ld) {
 #pragma unroll
             for (int i = 0; i < AV; ++i) {
                 const unsigned d = rowd[i];
                 const int iy = (int)((d >> 10) & 1023u) + dy - 1, ix = (int)(d & 1023u) - 1;
                 const bool ok = d != ~0u && (unsigned)iy < (unsigned)p.Hin && (unsigned)ix < (unsigned)p.Win;
-                offs[i] = ok ? (((int)(d >> 20) * p.Hin + iy) * p.Win + ix) * p.ld0 * (int)sizeof(T) + lane_k : OOB;
+                offs[i] = ok ? (((int)(d >> 20) * p.Hin + iy) * p.Win + ix) * ld * (int)sizeof(T) + lane_k : OOB;
             }
         };
         // A-piece offsets of filter tap (ty, tx): padding / upsampling / stride live here, once per tap
-        auto set_tap = [&](int ty, int tx) {
+        // (ld: pixel pitch of the source -- src0, or the tail source read at the tap (pad_t, pad_l), which is the output pixel: stride 1, no ups)
+        auto set_tap = [&](int ty, int tx, int ld) {
 #pragma unroll
             for (int i = 0; i < AV; ++i) {
                 const unsigned d = rowd[i];
@@ -468,7 +479,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                 int ix = (int)(d & 1023u) * p.stride - p.pad_l + tx;
                 const bool ok = d != ~0u && (unsigned)iy < (unsigned)Hv && (unsigned)ix < (unsigned)Wv;
                 if (p.ups) { iy >>= 1; ix >>= 1; }
-                offs[i] = ok ? (((int)(d >> 20) * p.Hin + iy) * p.Win + ix) * p.ld0 * (int)sizeof(T) + lane_k : OOB;
+                offs[i] = ok ? (((int)(d >> 20) * p.Hin + iy) * p.Win + ix) * ld * (int)sizeof(T) + lane_k : OOB;
             }
             if constexpr (A8) {
                 const unsigned d = srowd;
@@ -489,12 +500,23 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
         const bool x3 = X3OK && p.x3;
         int it = kb0_tiles, ity = 0, itx = 0, ic = 0, ph = 0;
         int ia = x3 ? kb0_tiles / 3 : kb0_tiles;          // (split-K ranges of the split mode start on a multiple of 3)
-        int hx_dx = 0, hx_ist = 0;                         // HX issue state: filter column of tile `it`, A stage of its group
+        int hx_dx = 0, hx_ist = 0, hx_len = 3;             // HX issue state: position of tile `it` in its group, A stage of the group, tiles per group
+        // the issue state moves to the tail source at its chunk c.  HX: a tail group is ONE tile -- the row-extended tile of srcx (filter row 1's
+        // pixels), multiplied at column offset 1 -- so that staging and fragment addressing stay what they are and only the group length differs
+        auto enter_tail = [&](int c) {
+            rsA = __builtin_amdgcn_make_buffer_rsrc((void*)p.srcx, 0, p.x_bytes, 0x00020000);
+            ic = c;
+            if constexpr (HX) { hx_len = 1; set_grp(1, p.ldx); }
+            else set_tap(p.pad_t, p.pad_l, p.ldx);
+        };
+        if (XT && kb0_tiles >= xt0) {                       // (a split-K slice may start inside the tail)
+            enter_tail(kb0_tiles - xt0);
+        } else
         if constexpr (HX) {
             const int grp = kb0_tiles / 3;                 // K order (dy, chunk, dx): group = dy * tpt + chunk
             ity = grp / tpt;
             ic = grp - ity * tpt;
-            set_grp(ity);
+            set_grp(ity, p.ld0);
         } else
         if (CONV) {
             const int ntap = p.KH * p.KW;
@@ -502,15 +524,19 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
             ic = p.korder ? ia / ntap : ia - tap * tpt;
             ity = tap / p.KW;
             itx = tap - ity * p.KW;
-            set_tap(ity, itx);
+            set_tap(ity, itx, p.ld0);
         }
         auto next_tile = [&]() {     // advance the issue state by one K tile
             ++it;
             if constexpr (HX) {
-                if (++hx_dx == 3) {
+                if (++hx_dx == hx_len) {
                     hx_dx = 0;
                     hx_ist ^= 1;
-                    if (++ic == tpt) { ic = 0; ++ity; set_grp(ity); }
+                    if (XT && it >= xt0) {
+                        if (it == xt0) enter_tail(0);
+                        else ++ic;
+                    } else
+                    if (++ic == tpt) { ic = 0; ++ity; set_grp(ity, p.ld0); }
                 }
                 return;
             }
@@ -520,13 +546,17 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
             }
             ++ia;
             if (CONV) {
+                if (XT && ia >= xt0) {
+                    if (ia == xt0) enter_tail(0);
+                    else ++ic;
+                } else
                 if (p.korder) {
                     if (++itx == p.KW) { itx = 0; if (++ity == p.KH) { ity = 0; ++ic; } }
-                    set_tap(ity, itx);
+                    set_tap(ity, itx, p.ld0);
                 } else if (++ic == tpt) {
                     ic = 0;
                     if (++itx == p.KW) { itx = 0; ++ity; }
-                    set_tap(ity, itx);
+                    set_tap(ity, itx, p.ld0);
                 }
             }
         };
@@ -698,7 +728,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
         int erow[TM];
         const char* hcb[TM];
         const char* hnb[TM];
-        int hcs[TM], hns[TM], m_dx = 0, m_st = 0;
+        int hcs[TM], hns[TM], m_dx = 0, m_st = 0, m_len = 3, m_t = kb0_tiles;          // (+ tiles per group -- 1 in the tail --, absolute index of that tile)
         const int ks_[4] = {(0 + lhalf) << 4, (2 + lhalf) << 4, (4 + lhalf) << 4, (6 + lhalf) << 4};          // k-step kk -> 16-byte slot 2 kk + half
         auto hx_set = [&](const char** hb, int* hs, int st, int dx) {
 #pragma unroll
@@ -714,8 +744,14 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                 const int pm = (wm * TM + i) * 32 + lrow, ir = pm / p.Wout;
                 erow[i] = ir * (p.Wout + 2) + (pm - ir * p.Wout);
             }
-            hx_set(hcb, hcs, 0, 0);
-            hx_set(hnb, hns, 0, 1);
+            if (XT && kb0_tiles >= xt0) {          // the slice starts inside the tail: every tile its own group, read at column offset 1
+                m_len = 1;
+                hx_set(hcb, hcs, 0, 1);
+                hx_set(hnb, hns, 1, 1);
+            } else {
+                hx_set(hcb, hcs, 0, 0);
+                hx_set(hnb, hns, 0, 1);
+            }
         }
         const char* const wbase = ldsB + (wn * TN) * 4096 + brow * 128;
         const char* curB = wbase + w_stage<W8>(kb0_tiles, 0) * BN * 128;
@@ -846,10 +882,12 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
             if (kt + 3 < nk) next_tile();
             const char* t = curA; curA = othA; othA = t;
             if constexpr (HX) {          // the tile multiplied next becomes current; its successor: next filter column, or column 0 of the next group's stage
-                if (++m_dx == 3) { m_dx = 0; m_st ^= 1; }
+                ++m_t;
+                if (++m_dx == m_len) { m_dx = 0; m_st ^= 1; if (XT && m_t >= xt0) m_len = 1; }
 #pragma unroll
                 for (int i = 0; i < TM; ++i) { hcb[i] = hnb[i]; hcs[i] = hns[i]; }
-                hx_set(hnb, hns, m_dx == 2 ? (m_st ^ 1) : m_st, m_dx == 2 ? 0 : m_dx + 1);
+                const bool glast = m_dx + 1 == m_len, ntail = XT && m_t + 1 >= xt0;          // the successor opens a group / is a tail tile
+                hx_set(hnb, hns, glast ? (m_st ^ 1) : m_st, ntail ? 1 : (glast ? 0 : m_dx + 1));
             }
             if constexpr (W8) {
                 ++t_abs;
@@ -1932,7 +1970,10 @@ static int launch_typed(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hi
             // K up to ~90 tiles: two co-resident 4-wave 128x160 blocks per CU (each other's prologue / epilogue cover) beat one
             // 8-wave 128x320 block in situ (sweep: -1.2 % per batch at 6000, worse again from 11520).  Also when K is
             // too short for split-K to bring the 128x320 grid to size (4096 x 1280 x 1280: 23 us, against 26 us on 128x128 tiles).
-            if (n320 && p.K <= 6000 && mt128 * (N / 160) >= 256) return launch_cfg<T, TO, 4, 1, 1, 5, W8>(d, p, conv, st);
+            // (a launch with a tail source is judged by its WINDOW's K: 16384 x 640 x 5760 + 320..1920 stays on the tile the sweep above chose for
+            //  the convolution it extends, instead of moving to 256x320 with split-K 2 -- partial sums the shorter loop never paid for)
+            const int k_rule = p.xt0 != 0x7fffffff ? p.xt0 * bk : p.K;
+            if (n320 && k_rule <= 6000 && mt128 * (N / 160) >= 256) return launch_cfg<T, TO, 4, 1, 1, 5, W8>(d, p, conv, st);
             // 64-128 tiles of 256 rows (the 3x3 convs of the 16x16 level, the long-K N = 640 convs of the 32x32 level): split-K 2-4 over the
             // 256-row tiles rather than 128-row tiles -- the 64x160 wave tile's main loop runs 1.0-1.25 PF where the 32x160 one stays below
             // 0.95 (6 KB of fragment reads per 5 MFMAs), and the fragment-ordered slabs keep the partial sums cheap
@@ -2000,12 +2041,24 @@ static int conv_gemm_impl(const rf_conv_gemm_desc* d, void* stream, int* plan) {
     RF_CHECK(w8 || d->ldw == 0 || (d->ldw >= (x3 ? 3 : 1) * d->K && d->ldw % vec == 0), "rf_conv_gemm: bad ldw=%d", d->ldw);
     RF_CHECK(!a8 || (d->ldw % 128 == 0 && d->ldw >= d->K), "rf_conv_gemm: fp8 x fp8 needs ldw (bytes) a multiple of 128 >= K");
     RF_CHECK(d->KH >= 1 && d->KW >= 1 && d->stride >= 1, "rf_conv_gemm: bad window");
-    RF_CHECK(d->KH * d->KW * ctot <= d->K && d->K < d->KH * d->KW * ctot + 8 * vec,
+    // centre-tap tail source: Cx more K elements behind the window's (kwin = the window's share of K)
+    const bool xt = d->srcx != nullptr;
+    RF_CHECK(!xt || ((d->dtype == RF_BF16 || h16) && d->w_dtype == 0 && d->batch == 1 && d->C1 == 0),
+             "rf_conv_gemm: a tail source (srcx) needs bf16 / fp16 operands and weights, one window source and batch 1 (dtype %d, w_dtype %d, C1 %d, batch %d)",
+             d->dtype, d->w_dtype, d->C1, d->batch);
+    RF_CHECK(!xt || (d->stride == 1 && d->ups == 0 && d->Hin == d->Hout && d->Win == d->Wout && d->KH * d->KW > 1),
+             "rf_conv_gemm: a tail source (srcx) needs a k x k window with stride 1, no ups and Hin x Win = Hout x Wout (stride %d, ups %d, %dx%d -> %dx%d)",
+             d->stride, d->ups, d->Hin, d->Win, d->Hout, d->Wout);
+    RF_CHECK(!xt || (d->Cx > 0 && d->Cx % (8 * vec) == 0 && d->Cx < d->K && d->ldx >= d->Cx && d->ldx % vec == 0 && (uintptr_t)d->srcx % 16 == 0),
+             "rf_conv_gemm: tail source: Cx=%d must be a multiple of %d below K=%d, ldx=%d a multiple of %d >= Cx, srcx 16-byte aligned", d->Cx, 8 * vec, d->K, d->ldx, vec);
+    const int kwin = xt ? d->K - d->Cx : d->K;
+    RF_CHECK(!xt || kwin == d->KH * d->KW * ctot, "rf_conv_gemm: with a tail source K=%d must be KH*KW*C0 + Cx = %d", d->K, d->KH * d->KW * ctot + d->Cx);
+    RF_CHECK(d->KH * d->KW * ctot <= kwin && kwin < d->KH * d->KW * ctot + 8 * vec,
              "rf_conv_gemm: K=%d inconsistent with KH*KW*(C0+C1)=%d", d->K, d->KH * d->KW * ctot);
     RF_CHECK(((uintptr_t)d->src0 | (uintptr_t)d->src1 | (uintptr_t)d->W) % 16 == 0, "rf_conv_gemm: operands must be 16-byte aligned");
     RF_CHECK(d->act != RF_ACT_GEGLU || (d->N % 64 == 0 && !d->rowvec), "rf_conv_gemm: GEGLU needs N %% 64 == 0 and no rowvec");
     RF_CHECK(!d->rowvec || d->rows_per_sample > 0, "rf_conv_gemm: rowvec needs rows_per_sample");
-    RF_CHECK(d->korder == 0 || ((d->korder == 1 || d->korder == 2) && ctot % (8 * vec) == 0 && d->K == d->KH * d->KW * ctot),
+    RF_CHECK(d->korder == 0 || ((d->korder == 1 || d->korder == 2) && ctot % (8 * vec) == 0 && kwin == d->KH * d->KW * ctot),
              "rf_conv_gemm: korder=%d needs (C0+C1) to be a multiple of %d", d->korder, 8 * vec);
     RF_CHECK(d->korder != 2 || ((d->dtype == RF_BF16 || h16) && d->out_dtype == d->dtype && d->w_dtype == 0 && d->C1 == 0 && d->batch == 1),
              "rf_conv_gemm: korder=2 (row-extended A tiles) is built for bf16 -> bf16 / fp16 -> fp16 convolutions of one source");
@@ -2059,9 +2112,14 @@ static int conv_gemm_impl(const rf_conv_gemm_desc* d, void* stream, int* plan) {
         const long long wb = (w8 || a8) ? (long long)d->N * p.ldw : ((long long)(d->N - 1) * p.ldw + (x3 ? 3 : 1) * d->K) * es;
         // ... and K tiles that never straddle a filter tap (uniform K offset per tile; rows packed as sample:12 | oy:10 | ox:10)
         const int bk = (int)(128 / es);
-        const bool uniform = d->K % bk == 0 && (!conv || (ctot % bk == 0 && d->K == d->KH * d->KW * ctot &&
+        const bool uniform = d->K % bk == 0 && (!conv || (ctot % bk == 0 && kwin == d->KH * d->KW * ctot &&
                                                          d->Hout <= 1024 && d->Wout <= 1024 && d->M / (d->Hout * d->Wout) < 4095));
-        p.glds = (d->C1 == 0 && uniform && ab < 0x7fff0000LL && wb < 0x7fff0000LL) ? 1 : 0;
+        const long long xb = xt ? ((rows_a - 1) * d->ldx + d->Cx) * es : 0;
+        p.glds = (d->C1 == 0 && uniform && ab < 0x7fff0000LL && wb < 0x7fff0000LL && xb < 0x7fff0000LL) ? 1 : 0;
+        RF_CHECK(!xt || (conv && p.glds), "rf_conv_gemm: a tail source (srcx) needs the direct-to-LDS main loop (C0 a multiple of the K tile, 31-bit operand extents)");
+        p.srcx = d->srcx; p.ldx = d->ldx;
+        p.xt0 = xt ? kwin / bk : 0x7fffffff;
+        p.x_bytes = (unsigned)xb;
         p.korder = d->korder;
         p.a_bytes = (unsigned)(p.glds ? ab : 0);
         p.w_bytes = (unsigned)(p.glds ? wb : 0);

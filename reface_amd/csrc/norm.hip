@@ -351,7 +351,9 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ x
 using namespace rf;
 
 extern "C" const char* rf_last_error(void) { return rf::g_err; }
-extern "C" int rf_version(void) { return 101; }          // 101: RF_F16 (the fp16 throughput mode), `dtype` in rf_ffn_desc / rf_stem_desc / rf_gn_silu_conv3x3_small
+// 101: RF_F16 (the fp16 throughput mode), `dtype` in rf_ffn_desc / rf_stem_desc / rf_gn_silu_conv3x3_small
+// 102: rf_conv_gemm_desc gained the trailing srcx / Cx / ldx (centre-tap tail source)
+extern "C" int rf_version(void) { return 102; }
 
 static int gn_check(const char* name, int dtype, int C, int ldx, int nchunks) {
     const int vec = dtype == RF_F32 ? 4 : 8;

@@ -369,9 +369,9 @@ def _default_workspace(device):
 def conv_gemm(src0, W, out, *, M, N, K, C0, ld0, src1=None, C1=0, ld1=0, Hin=1, Win=1, Hout=1, Wout=1, KH=1, KW=1,
               stride=1, pad_t=0, pad_l=0, ups=0, bias=None, rowvec=None, rows_per_sample=0, ldv=0, residual=None, ldr=0,
               act=ACT_NONE, ldo=None, alpha=1.0, batch=1, sA=0, sW=0, sO=0, sR=0, ldw=0, act_vec=None, korder=0, workspace=None, x3=False,
-              name="rf_conv_gemm"):
+              srcx=None, Cx=0, ldx=0, name="rf_conv_gemm"):
     """Prepare an rf_conv_gemm launch (see include/reface_hip.h).  x3: split-bf16 operands (src0 = [.., C0 hi | C0 lo] bf16, W from
-    pack_x3, fp32 out); K / C0 are the REAL sizes."""
+    pack_x3, fp32 out); K / C0 are the REAL sizes.  srcx / Cx / ldx: the centre-tap tail source (K counts its Cx channels)."""
     lib = _lib.load()
     a8 = None
     if isinstance(src0, Fp8Act):          # fp8 activations + block scales: K / C0 / ld0 are the PADDED byte counts (the caller passes them)
@@ -414,9 +414,13 @@ def conv_gemm(src0, W, out, *, M, N, K, C0, ld0, src1=None, C1=0, ld1=0, Hin=1, 
     d.batch, d.sA, d.sW, d.sO, d.sR = batch, sA, sW, sO, sR
     d.act_vec = _p(act_vec)
     d.korder = korder
+    if srcx is not None:
+        _require_gpu(srcx)
+        assert a8 is None and srcx.dtype == src0.dtype
+        d.srcx, d.Cx, d.ldx = _p(srcx), Cx, ldx
     ws = workspace if workspace is not None else _default_workspace(src0.device)
     d.workspace, d.workspace_bytes = _p(ws), (ws.numel() * ws.element_size() if ws is not None else 0)
-    l = Launch(lib.rf_conv_gemm, (C.byref(d),), (d, src0, src1, W, out, bias, rowvec, residual, act_vec, ws, wq, a8, oq), name)
+    l = Launch(lib.rf_conv_gemm, (C.byref(d),), (d, src0, src1, W, out, bias, rowvec, residual, act_vec, ws, wq, a8, oq, srcx), name)
     if wq is not None and a8 is None:
         # fp8 weights run only on the direct-to-LDS main loop, whose preconditions (one source, 31-bit operand extents, <= 1024^2 outputs,
         # < 4095 samples, whole K tiles per tap) depend on the launch, not only on the weight: ask the library, and give a layer that
@@ -529,10 +533,12 @@ def conv3x3_stem(x, W, bias, out, *, dup=None, name="conv_in"):
 
 
 def conv2d(x, W, out, bias=None, *, ksize=3, stride=1, pad=(1, 1), ups=0, x2=None, residual=None, rowvec=None,
-           act=ACT_NONE, act_vec=None, korder=0, x3=False, name="conv2d"):
+           act=ACT_NONE, act_vec=None, korder=0, x3=False, tail=None, name="conv2d"):
     """Channels-last convolution.  x: [B, Hin, Win, C0] (+ optional x2 [B, Hin, Win, C1] concatenated
     on channels); W: packed [Cout, k*k*(C0+C1)]; out: [B, Hout, Wout, Cout].  x3: x is the split-bf16 form [B, Hin, Win, 2*C0] of an
-    fp32 tensor and W comes from pack_x3 ([Cout, 3*k*k*C0])."""
+    fp32 tensor and W comes from pack_x3 ([Cout, 3*k*k*C0]).
+    tail: a second tensor [B, Hout, Wout, Cx] whose 1x1 convolution is summed into the same contraction (rf_conv_gemm_desc.srcx: the ResBlock's
+    skip_connection inside out_layers.3) -- W is then pack_conv_tail(W, w_1x1) = [Cout, k*k*C0 + Cx] and `bias` the sum of the two biases."""
     if isinstance(x, Fp8Act):             # C0 = the padded channel count (W from quantize_fp8_padded(w, k*k, C))
         B, Hin, Win, C0 = x.q.shape
         ld0 = x.q.stride(2)
@@ -547,11 +553,24 @@ def conv2d(x, W, out, bias=None, *, ksize=3, stride=1, pad=(1, 1), ups=0, x2=Non
     if x3:
         assert x2 is None and C0 % 2 == 0 and K % 3 == 0
         C0, K = C0 // 2, K // 3
+    tkw = {}
+    if tail is not None:
+        assert isinstance(tail, torch.Tensor) and x2 is None and not x3 and tail.shape[:3] == out.shape[:3] and tail.stride(3) == 1
+        assert tail.stride(1) == Wout * tail.stride(2) and (B == 1 or tail.stride(0) == Hout * tail.stride(1)), "tail source: uniform pixel pitch"
+        assert K == ksize * ksize * C0 + tail.shape[3], (K, ksize, C0, tail.shape[3])
+        tkw = dict(srcx=tail, Cx=tail.shape[3], ldx=tail.stride(2))
     return conv_gemm(x, W, out, M=B * Hout * Wout, N=N, K=K, C0=C0, ld0=ld0, src1=x2, C1=C1,
                      ld1=(x2.stride(2) if x2 is not None else 0), Hin=Hin, Win=Win, Hout=Hout, Wout=Wout, KH=ksize, KW=ksize,
                      stride=stride, pad_t=pad[0], pad_l=pad[1], ups=ups, bias=bias, residual=residual,
                      ldr=(residual.stride(2) if residual is not None else 0), rowvec=rowvec, rows_per_sample=Hout * Wout,
-                     ldv=(rowvec.stride(0) if rowvec is not None else 0), act=act, act_vec=act_vec, ldo=out.stride(2), korder=korder, x3=x3, name=name)
+                     ldv=(rowvec.stride(0) if rowvec is not None else 0), act=act, act_vec=act_vec, ldo=out.stride(2), korder=korder, x3=x3, name=name, **tkw)
+
+
+def pack_conv_tail(wp, w_tail):
+    """[Cout, K] packed window weights (pack_conv_weight, any korder) + [Cout, Cx] 1x1 weights -> [Cout, K + Cx]: the W operand of a
+    convolution with a centre-tap tail source (conv2d(..., tail=...))."""
+    assert wp.shape[0] == w_tail.shape[0] and w_tail.dim() == 2
+    return torch.cat([wp, w_tail.to(wp.dtype)], 1).contiguous()
 
 
 GN_MAX_CHUNKS = 32

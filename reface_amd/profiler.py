@@ -33,7 +33,7 @@ def gemm_flops(l):
     if l.fn.__name__ != "rf_conv_gemm":
         return 0.0
     d = l.keep[0]
-    k_real = d.KH * d.KW * (d.C0 + d.C1)
+    k_real = d.KH * d.KW * (d.C0 + d.C1) + (d.Cx if d.srcx else 0)          # (+ the centre-tap tail source's channels)
     if d.dtype == 2:            # fp8 activations: C0 / K count the channel run PADDED to 128; the algorithmic count uses the real channels
         k_real = d.KH * d.KW * next((k.C for k in l.keep if type(k).__name__ == "Fp8Act"), d.C0)
     return 2.0 * d.M * d.N * min(k_real, d.K) * d.batch

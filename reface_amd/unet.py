@@ -140,6 +140,7 @@ class UNetEngine:
         self.gn_fold_maxc = int(os.environ.get("REFACE_GN_FOLD_MAXC", "640"))
         self.n_gn_folded = 0
         self.n_hx = 0
+        self.n_skip_folded = 0          # ResBlocks whose skip_connection runs inside out_layers.3 (_res)
         self.n_ln_folded = 0
         self.n_cu = torch.cuda.get_device_properties(device).multi_processor_count if torch.cuda.is_available() else 256
         self.gn_fused = 0
@@ -301,9 +302,20 @@ class UNetEngine:
         return self.ctx_table[:, off:off + c]
 
     # ------------------------------------------------------------------ main graph
-    def _conv3(self, x, wkey, out, bkey, name, **kw):
-        """3x3 conv launch; K order chosen per layer (ops.conv_korder)."""
+    def _conv3(self, x, wkey, out, bkey, name, tail=None, **kw):
+        """3x3 conv launch; K order chosen per layer (ops.conv_korder).
+        tail = (xt, wkey_1x1, bkey_1x1): the 1x1 convolution of xt rides in the same contraction (ops.conv2d's tail source; 16-bit modes) -- the
+        packed weight is [W (the K order chosen here) | W_1x1], the bias the fp32 sum of the two."""
         cin = x.shape[3]
+        if tail is not None:
+            assert self.dt in H16 and not self.w8 and not self.x3 and not isinstance(x, ops.Fp8Act)
+            xt, tkey, tbkey = tail
+            kw = dict(kw, tail=xt)
+            bias = self._packed(bkey, ("+", tbkey), lambda: (self.sd[bkey] + self.sd[tbkey]).contiguous())
+            wtail = lambda wp: ops.pack_conv_tail(wp, self.sd[tkey].reshape(out.shape[3], xt.shape[3]))
+            tk = ("tail", tkey)
+        else:
+            bias, wtail, tk = self.f32(bkey), (lambda wp: wp), ()
         if isinstance(x, ops.Fp8Act):
             return ops.conv2d(x, self.gw8(ops.pack_conv_weight(self.sd[wkey], F32), 9, cin), out, self.f32(bkey), name=name, **kw)
         if self.x3 and x.dtype == torch.bfloat16:          # split-bf16 input (from _gn(split=True) / split_in): cin is half the stored width
@@ -315,7 +327,8 @@ class UNetEngine:
             # 3x3 stride-1 convolution: K order (filter row, channel chunk, filter column) -- one row-extended A tile serves the three horizontal
             # taps (a third of the A-operand fill, gemm.hip HX).  Whether the launch's tile can take it (whole image rows per tile) is the
             # library's answer: ask for the plan, fall back to the tap-major order otherwise.
-            cand = ops.conv2d(x, self._packed(wkey, "hx", lambda: ops.pack_conv_weight(self.sd[wkey], self.dt, korder=2)), out, self.f32(bkey), korder=2, name=name, **kw)
+            cand = ops.conv2d(x, self._packed(wkey, ("hx",) + tk if tk else "hx", lambda: wtail(ops.pack_conv_weight(self.sd[wkey], self.dt, korder=2))), out, bias, korder=2,
+                              name=name, **kw)
             try:
                 ops.gemm_plan2(cand)
                 self.n_hx += 1
@@ -324,8 +337,11 @@ class UNetEngine:
                 pass
         def pack():
             wp = ops.pack_conv_weight(self.sd[wkey], F32, korder=ko)
-            return wp.to(self.dt) if ko else self.gw(wp, cin)
-        return ops.conv2d(x, self._packed(wkey, ("tap", ko), pack), out, self.f32(bkey), korder=ko, name=name, **kw)
+            return wtail(wp.to(self.dt) if ko or tk else self.gw(wp, cin))
+        l = ops.conv2d(x, self._packed(wkey, ("tap", ko) + tk, pack), out, bias, korder=ko, name=name, **kw)
+        if tk:
+            ops.gemm_plan2(l)          # (a launch the library cannot run with its tail source fails here, not at the first replay)
+        return l
 
     def _packed(self, wkey, kind, make):
         """One packed device copy per (weight, packing): a convolution launched in two sample slices (_add_conv3) shares it."""
@@ -334,7 +350,7 @@ class UNetEngine:
             w = self._wpack[(wkey, kind)] = make()
         return w
 
-    def _add_conv3(self, x, wkey, out, bkey, name, rowvec=None, residual=None, **kw):
+    def _add_conv3(self, x, wkey, out, bkey, name, rowvec=None, residual=None, tail=None, **kw):
         """_conv3 + _add, with the launch split BY SAMPLES when its 256-row tiles overhang a whole number of rounds of the chip by a little
         (768x768: 8 samples x 36 tiles = 288 = 1.125 rounds of 256 CUs -- the library then falls back to quarter tiles for the whole launch):
         the first k samples fill whole rounds of big tiles, the rest is a launch of its own (its plan: smaller tiles / split-K).
@@ -353,7 +369,7 @@ class UNetEngine:
                     if not (0 < k < B and k * ps >= 0.9 * self.n_cu * full):
                         k = 0
         if not k:
-            return self._add(self._conv3(x, wkey, out, bkey, name, **dict(kw, **({"rowvec": rowvec} if rowvec is not None else {}),
+            return self._add(self._conv3(x, wkey, out, bkey, name, tail=tail, **dict(kw, **({"rowvec": rowvec} if rowvec is not None else {}),
                                                                            **({"residual": residual} if residual is not None else {}))), out)
         self.n_sample_split += 1
         for a, b in ((0, k), (k, B)):
@@ -362,7 +378,7 @@ class UNetEngine:
                 kws["rowvec"] = rowvec[a:b]
             if residual is not None:
                 kws["residual"] = residual[a:b]
-            self._add(self._conv3(x[a:b], wkey, out[a:b], bkey, f"{name}[{a}:{b}]", **kws), out[a:b])
+            self._add(self._conv3(x[a:b], wkey, out[a:b], bkey, f"{name}[{a}:{b}]", tail=(None if tail is None else (tail[0][a:b],) + tuple(tail[1:])), **kws), out[a:b])
 
     def _add(self, launch, out=None):
         """Append a launch; GEMM outputs are remembered so that a later GroupNorm can ask their producers for its statistics."""
@@ -415,6 +431,17 @@ class UNetEngine:
         (self.aput if self.a8 else self.pool.put)(t1)
         t2 = self._gn(h1, f"{p}.out_layers.0", 1e-5, True, fp8=self.a8, split=self.x3_ok(9 * cout, cout))
         self.pool.put(h1)
+        # 16-bit modes: the 1x1 skip_connection runs inside out_layers.3 -- one contraction over [im2col(t2) | x] (rf_conv_gemm's tail source):
+        # no launch of its own, no `skip` tensor written and re-read as the residual.  fp32 / f32x3 / fp8 keep the chain below.
+        fold = (cin != cout and self.dt in H16 and not self.w8 and not self.a8 and not self.x3 and cin % 64 == 0 and cout % 64 == 0
+                and x.stride(3) == 1 and x.stride(1) == W * x.stride(2) and x.stride(0) == H * x.stride(1) and B * H * W * x.stride(2) * 2 < 0x7fff0000)
+        if fold:
+            y = dst if dst is not None else self.pool.get((B, H, W, cout), self.dt)
+            self._add_conv3(t2, f"{p}.out_layers.3.weight", y, f"{p}.out_layers.3.bias", f"{p}.out_layers.3",
+                            tail=(x, f"{p}.skip_connection.weight", f"{p}.skip_connection.bias"))
+            self.pool.put(t2)
+            self.n_skip_folded += 1
+            return y
         if cin != cout:
             skip = self.pool.get((B, H, W, cout), self.dt)
             w_sk = self.sd[f"{p}.skip_connection.weight"].reshape(cout, cin)
