@@ -455,6 +455,18 @@ int rf_align_quad_u8(const void* frames_u8, int B, int H, int W, int Cf, int64_t
                      void* out_u8, void* stream);
 int rf_resample_u8(const void* x_u8, int B, int H, int W, int C, const int* xbounds, const int* xk, int xksize, const int* ybounds, const int* yk,
                    int yksize, void* tmp_u8, void* out_u8, int h, int w, void* stream);
+/*
+ * The video dataset's per-frame preparation (ldm/data/video_swap_dataset.py:135-240) in one launch and one pass over the crops:
+ *   rf_video_prep_u8 : crops u8 [B, Hc, Wc, 3] (C must be 3), labels u8 [B, h, w], lut256 u8 [256] (non-zero = a label that is cut out) and the
+ *                      two tap tables of rf_resample_u8 (x: Wc -> w, y: Hc -> h; reface_amd.align.resample_taps, "bicubic" for PIL's default
+ *                      Image.resize) -> target fp32 [B, 3, h, w] = (resized / 255 - 0.5) / 0.5, mask fp32 [B, 1, h, w] = 1 - (lut[label] != 0),
+ *                      inpaint fp32 [B, 3, h, w] = target * mask.  The resize is PIL's two integer passes (u8 between them) done in LDS: the
+ *                      resized u8 image is never written to memory.  Bit for bit what the host dataset computes.  Tap windows are clipped to
+ *                      the axis; any ratio >= 1 and any h, w.  The three outputs are distinct buffers that overlap neither input.
+ */
+int rf_video_prep_u8(const void* crops_u8, int B, int Hc, int Wc, int C, const void* labels_u8, const void* lut256_u8, const int* xbounds,
+                     const int* xk, int xksize, const int* ybounds, const int* yk, int yksize, float* target, float* mask, float* inpaint, int h, int w,
+                     void* stream);
 /* elementwise y = silu(x) on fp32 (emb path, openaimodel.py:219) */
 int rf_silu_f32(const float* x, float* y, int64_t n, void* stream);
 

@@ -123,18 +123,34 @@ def _lanczos(x):
     return sinc(x) * sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
 
 
+def _bicubic(x, a=-0.5):
+    x = -x if x < 0.0 else x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+_FILTERS = {"lanczos": (_lanczos, 3.0), "bicubic": (_bicubic, 2.0)}          # Resample.c: the filter function and its support
+
+
 @functools.lru_cache(maxsize=64)
-def resample_taps(n_in, n_out):
-    """PIL's LANCZOS tap table of one axis resized n_in -> n_out (Resample.c: precompute_coeffs + normalize_coeffs_8bpc), in Python floats:
+def resample_taps(n_in, n_out, filter="lanczos"):
+    """PIL's tap table of one axis resized n_in -> n_out (Resample.c: precompute_coeffs + normalize_coeffs_8bpc), in Python floats, for the
+    LANCZOS filter or for BICUBIC (``filter="bicubic"``: what Image.resize takes when it is given no filter):
     bounds int32 [n_out, 2] = (first input index, tap count) and taps int32 [n_out, ksize], 22-bit fixed point.  An unchanged axis
     (PIL skips its pass) gets the identity table."""
     n_in, n_out = int(n_in), int(n_out)
+    if filter not in _FILTERS:
+        raise ValueError(f"resample_taps: filter must be one of {sorted(_FILTERS)}, got {filter!r}")
+    fn, fsupport = _FILTERS[filter]
     if n_in == n_out:
         return np.stack([np.arange(n_out), np.ones(n_out, dtype=np.int64)], 1).astype(np.int32), np.full((n_out, 1), 1 << PRECISION_BITS, dtype=np.int32)
     scale = filterscale = n_in / n_out
     if filterscale < 1.0:
         filterscale = 1.0
-    support = 3.0 * filterscale
+    support = fsupport * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     bounds = np.zeros((n_out, 2), dtype=np.int32)
     taps = np.zeros((n_out, ksize), dtype=np.int32)
@@ -143,7 +159,7 @@ def resample_taps(n_in, n_out):
         center = (i + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)
         xmax = min(int(center + support + 0.5), n_in) - xmin
-        w = [_lanczos((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        w = [fn((x + xmin - center + 0.5) * ss) for x in range(xmax)]
         ww = 0.0
         for v in w:
             ww += v
@@ -170,8 +186,8 @@ def load_image(path_or_array):
 
 class Aligner:
     """The device half of the alignment: ``align(frames, landmarks)`` -> (crops uint8 [B, S, S, 3] on the device, quads fp64 [B, 4, 2]).
-    Frames are uint8 HWC arrays (RGB or RGBA; alpha is not read: the reference keeps ``crop.convert("RGB")``, and its frames are opaque) or
-    image paths; frames of one size share one launch, and those whose plan shrinks go through the LANCZOS resampler first."""
+    Frames are uint8 HWC arrays (RGB or RGBA; alpha is not read: the reference keeps ``crop.convert("RGB")``, and its frames are opaque), image
+    paths, or uint8 HWC tensors that are on the device already (they are not copied to the host); frames of one size share one launch, and those whose plan shrinks go through the LANCZOS resampler first."""
 
     def __init__(self, output_size=1024, enable_padding=False, device="cuda"):
         if enable_padding:
@@ -186,6 +202,8 @@ class Aligner:
         return self._taps[key]
 
     def _upload(self, arrays):
+        if torch.is_tensor(arrays[0]):          # frames that are on the device already stay there
+            return torch.stack([a.to(self.device) for a in arrays])
         return torch.from_numpy(np.stack(arrays)).pin_memory().to(self.device, non_blocking=True)
 
     def resize(self, frames_u8, size):
@@ -198,7 +216,7 @@ class Aligner:
         return out
 
     def align(self, frames, landmarks=None, quads=None, scale=1.0):
-        frames = [load_image(f) for f in frames]
+        frames = [f if torch.is_tensor(f) else load_image(f) for f in frames]
         if (landmarks is None) == (quads is None):
             raise ValueError("Aligner.align takes either landmarks [B, 68, 2] or quads [B, 4, 2]")
         if quads is None:
@@ -212,7 +230,7 @@ class Aligner:
         groups = {}
         for i, (f, p) in enumerate(zip(frames, plans)):
             if p.shrink > 1:
-                groups.setdefault((f.shape, p.rsize), []).append(i)
+                groups.setdefault((tuple(f.shape), p.rsize), []).append(i)
         for (_, rsize), members in groups.items():
             small = self.resize(self._upload([frames[i] for i in members]), rsize)
             for k, i in enumerate(members):

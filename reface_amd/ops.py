@@ -972,6 +972,26 @@ def resample_u8(x_u8, xtaps, ytaps, tmp, out, name="resample_u8"):
                   (x_u8, xb, xk, yb, yk, tmp, out), name)
 
 
+def video_prep_u8(crops_u8, labels_u8, lut256, xtaps, ytaps, target, mask, inpaint, name="video_prep_u8"):
+    """The video dataset's item preparation in one launch (rf_video_prep_u8): crops uint8 [B, Hc, Wc, 3] resized to (h, w) with PIL's two-pass
+    integer resampler (xtaps / ytaps as for resample_u8; reface_amd.align.resample_taps(..., "bicubic") is Image.resize's default), then
+    target fp32 [B, 3, h, w] = (resized / 255 - 0.5) / 0.5, mask fp32 [B, 1, h, w] = 1 - (lut256[labels] != 0) from labels uint8 [B, h, w],
+    inpaint = target * mask -- bit for bit what reface_amd.data.VideoDataset builds on the host."""
+    lib = _lib.load()
+    (xb, xk), (yb, yk) = xtaps, ytaps
+    _require_gpu(crops_u8, labels_u8, lut256, xb, xk, yb, yk, target, mask, inpaint)
+    B, Hc, Wc, Cc = crops_u8.shape
+    h, w = target.shape[2], target.shape[3]
+    assert crops_u8.dtype == labels_u8.dtype == lut256.dtype == torch.uint8 and crops_u8.is_contiguous() and labels_u8.is_contiguous()
+    assert lut256.is_contiguous() and lut256.numel() == 256 and labels_u8.shape == (B, h, w)
+    for t, c in ((target, 3), (mask, 1), (inpaint, 3)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == (B, c, h, w), tuple(t.shape)
+    for b, k, n in ((xb, xk, w), (yb, yk, h)):
+        assert b.dtype == k.dtype == torch.int32 and b.is_contiguous() and k.is_contiguous() and b.shape == (n, 2) and k.ndim == 2 and k.shape[0] == n
+    return Launch(lib.rf_video_prep_u8, (_p(crops_u8), B, Hc, Wc, Cc, _p(labels_u8), _p(lut256), _p(xb), _p(xk), xk.shape[1], _p(yb), _p(yk), yk.shape[1],
+                                         _p(target), _p(mask), _p(inpaint), h, w), (crops_u8, labels_u8, lut256, xb, xk, yb, yk, target, mask, inpaint), name)
+
+
 def label_mask(labels_u8, lut256, out, *, invert, name="label_mask"):
     lib = _lib.load()
     _require_gpu(labels_u8, lut256, out)

@@ -61,6 +61,33 @@ def load_frame(frames_dir, sid):
     return np.asarray(im, dtype=np.uint8)
 
 
+def paste_on_device(result01, coeffs, frames, crop_size=CROP_SIZE, channels=4):
+    """The device half of stage 3 for frames that are on the device already: run_batch's fp32 [B, 3, h, w] result, the frames' inverse
+    transforms (fp64 [B, 8], host) and B uint8 device tensors [H, W, 3 | 4] (sizes and channel counts may differ within the batch) ->
+    (pasted frames: B uint8 device tensors [H, W, channels]; the enlarged crops uint8 [B, S, S, 3] on the device -- the bytes of
+    ``model_outputs/<id>.png``).  Nothing is copied to or from the host except the 8 coefficients per frame."""
+    B, S = result01.shape[0], int(crop_size)
+    if len(frames) != B or len(coeffs) != B:
+        raise ValueError(f"{len(frames)} frames and {len(coeffs)} transforms for a batch of {B}")
+    dev = result01.device
+    crops = torch.empty((B, S, S, 3), dtype=torch.uint8, device=dev)
+    ops.paste_crop_u8(result01.float().contiguous(), crops)()
+    co = torch.from_numpy(np.ascontiguousarray(coeffs, dtype=np.float64).reshape(B, 8)).to(dev)
+    out = [None] * B
+    groups = {}
+    for i, f in enumerate(frames):          # one launch per frame size (all frames of a video share one)
+        groups.setdefault(tuple(f.shape), []).append(i)
+    for shape, members in groups.items():
+        whole = len(members) == B
+        sel = torch.tensor(members, device=dev)
+        fr = torch.stack([frames[i] for i in members])
+        o = torch.empty(fr.shape[:3] + (int(channels),), dtype=torch.uint8, device=dev)
+        ops.paste_back_u8(crops if whole else crops.index_select(0, sel).contiguous(), co if whole else co.index_select(0, sel).contiguous(), fr, o)()
+        for k, i in enumerate(members):
+            out[i] = o[k]
+    return out, crops
+
+
 class PasteBack:
     """The device half of stage 3 for one video: ``prefetch(ids)`` starts decoding the frames of a batch on a thread pool; ``paste(result01,
     ids)`` turns run_batch's fp32 [B, 3, h, w] result into the pasted frames (uint8 [H, W, channels] host arrays, one per id)."""
@@ -100,6 +127,18 @@ class PasteBack:
             for k, i in enumerate(members):
                 out[i] = host[k]
         return out
+
+    def paste_device(self, result01, ids, frames):
+        """``paste`` for frames that are on the device already (B uint8 device tensors [H, W, 3 | 4]): the pasted frames stay there too
+        (B uint8 device tensors [H, W, channels]); the same bytes as ``paste``."""
+        ids = list(ids)
+        if len(ids) != result01.shape[0]:
+            raise ValueError(f"{len(ids)} ids for a batch of {result01.shape[0]}")
+        idx = [int(s) for s in ids]
+        bad = [s for s, i in zip(ids, idx) if not 0 <= i < len(self.coeffs)]
+        if bad:
+            raise IndexError(f"frames {bad} have no inverse transform ({len(self.coeffs)} in the file)")
+        return paste_on_device(result01, self.coeffs[idx], frames, crop_size=self.S, channels=self.channels)[0]
 
     def close(self):
         self.pool.shutdown(wait=True)

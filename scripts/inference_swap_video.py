@@ -34,6 +34,14 @@ Landmarks come from ``--landmarks FILE.npy`` ([N, 68, 2]) and ``--src_landmarks 
 (landmark detection is not built).  A frame whose landmarks are not finite ("no face") repeats the previous frame's crop and transform, as
 the reference's ``except`` branch does.  ``--align --parse_masks --paste_back`` together run raw frames to pasted frames in one command.
 
+``--stream`` does the work of ``--align --parse_masks --paste_back`` as one device-resident chain (reface_amd/stream.py): every frame is decoded
+once (by the loader's workers), uploaded once, aligned, parsed, turned into the model's input tensors (rf_video_prep_u8: the dataset's
+``__getitem__`` on the GPU, bit for bit), swapped and pasted without leaving the device, and encoded once (``results/<id>.png``) off the launch
+thread.  It reads what the three flags read and writes ``results/``, ``<video>_inv_transforms.npy`` and the source's two files under
+``temp_results/`` -- the same bytes as the staged route -- but not ``<video>cropped_face/``, ``<video>mask_frames/`` or ``model_outputs/``;
+``--stream_keep`` writes those three too, from the device bytes, for the frames that are swapped (the staged route also aligns and parses the
+trailing frames that ``drop_last`` never swaps; the stream does not decode them).
+
 The mp4 + audio mux of stage 3 is not built (no video encoder in this build).
 """
 import argparse
@@ -104,6 +112,11 @@ def build_parser():
     p.add_argument("--landmarks", type=str, default=None, help="--align: .npy of the frames' landmarks [N, 68, 2] (non-finite row = no face); "
                    "without it they come from dlib")
     p.add_argument("--src_landmarks", type=str, default=None, help="--align: .npy of --src_image's landmarks [68, 2]; without it they come from dlib")
+    p.add_argument("--stream", action="store_true", help="raw frames to pasted frames as one device-resident chain: the work of --align --parse_masks "
+                   "--paste_back with one PNG decode and one encode per frame and no intermediate files (reads what they read; writes results/, "
+                   "<video>_inv_transforms.npy and temp_results/)")
+    p.add_argument("--stream_keep", action="store_true", help="--stream: also write <video>cropped_face/, <video>mask_frames/ and model_outputs/ "
+                   "of the swapped frames, from the device bytes, off the launch thread")
     return p
 
 
@@ -162,7 +175,7 @@ def check_align_inputs(opt):
                 continue
             lm, src_lm = (got, src_lm) if files is paths else (lm, got)
     if problems:
-        raise SystemExit("inference_swap_video: --align needs the full frames, the source image and 68 landmarks for each; problems:\n  " +
+        raise SystemExit(f"inference_swap_video: {'--stream' if getattr(opt, 'stream', False) else '--align'} needs the full frames, the source image and 68 landmarks for each; problems:\n  " +
                          "\n  ".join(problems[:8]) + (f"\n  ... and {len(problems) - 8} more" if len(problems) > 8 else ""))
     return paths, lm, src_lm
 
@@ -180,9 +193,106 @@ def run_align(opt, paths, lm, src_lm):
           f"repeat the previous one); inverse transforms in {pasteback_paths(opt)['inv_transforms']}")
 
 
+def load_model_and_sampler(opt, config):
+    """The model of --config / --ckpt on the GPU in --precision, and its DDIM / PLMS sampler."""
+    if opt.clip_vision_config:
+        import json
+        config.model.params.cond_stage_config["params"] = {"vision_config": json.loads(opt.clip_vision_config)}
+    model = load_model_from_config(config, opt.ckpt)
+    device = torch.device("cuda")
+    if opt.precision in ("autocast", "bf16"):
+        model.set_compute_dtype(torch.bfloat16, encoders=True)
+    elif opt.precision == "fp16":                   # the bf16 mode's UNet kernels on fp16 storage / MFMA (same speed, ~17 dB closer to the exact-fp32 image);
+        model.set_compute_dtype(torch.float16)      # the towers and the VAE encoder stay fp32: this mode is chosen for its distance to "full"
+    elif opt.precision == "fp8":
+        model.set_compute_dtype("fp8", encoders=True)
+    elif opt.precision == "fullx3":                 # the fast form of "full": fp32 storage, split-bf16 GEMM operands (3 bf16 MFMA passes)
+        model.set_compute_dtype("f32x3")
+    if opt.plms:
+        from ldm.models.diffusion.plms import PLMSSampler
+        sampler = PLMSSampler(model)
+    else:
+        sampler = DDIMSampler(model)
+    return model, sampler, device
+
+
+def run_stream(opt):
+    """--stream: frames -> pasted frames with every intermediate on the device (reface_amd/stream.py)."""
+    from reface_amd.data import load_source_reference, raw_collate
+    from reface_amd.stream import FrameDataset, VideoStream, stream_paths
+    paths, lm, src_lm = check_align_inputs(opt)
+    config = rcfg.load(opt.config)
+    test_args = dict(config.data.params.test.params)
+    remove = test_args["remove_mask_tar_FFHQ"] if test_args["gray_outer_mask"] else [2, 3, 5, 6, 7]
+    vs = VideoStream(lm, remove, seg_ckpt=opt.faceParsing_ckpt, seg12=opt.seg12)          # host fp64 only: quads and inverse transforms of EVERY frame
+    pp, sp = prepared_paths(opt), pasteback_paths(opt)
+    np.save(sp["inv_transforms"], vs.inv_transforms)
+    torch.manual_seed(opt.seed)
+    np.random.seed(opt.seed)
+    torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
+    # the ONE source image stays on the staged code: its crop and label map as files, read back by load_source_reference
+    from reface_amd.align import align_to_disk
+    from reface_amd.parsing import FaceParser, parse_label_maps
+    os.makedirs(os.path.dirname(pp["src"]), exist_ok=True)
+    align_to_disk([opt.src_image], src_lm, [pp["src"]])
+    vs.parser = FaceParser(opt.faceParsing_ckpt)
+    parse_label_maps([(pp["src"], pp["src_mask"])], opt.faceParsing_ckpt, seg12=opt.seg12, parser=vs.parser)
+    model, sampler, device = load_model_and_sampler(opt, config)
+    from reface_amd.pasteback import PngWriter
+    from reface_amd.pipeline import SwapRunner
+    runner = SwapRunner(model, sampler, opt)
+    results = os.path.join(opt.outdir, "results")
+    os.makedirs(results, exist_ok=True)
+    keep = stream_paths(opt.Base_dir, opt.target_video, opt.outdir) if opt.stream_keep and not opt.skip_save else None
+    for d in (keep or {}).values():
+        os.makedirs(d, exist_ok=True)
+    ref1 = load_source_reference(pp["src"], pp["src_mask"], test_args["preserve_mask_src_FFHQ"]).to(device)
+    ns = max(1, opt.n_samples)
+    ds = FrameDataset(sp["video_frames"], len(paths) // ns * ns)          # drop_last: the trailing partial batch is never swapped, so never decoded
+    loader = torch.utils.data.DataLoader(ds, batch_size=ns, num_workers=opt.num_workers, pin_memory=True, shuffle=False, drop_last=True,
+                                         collate_fn=raw_collate)
+    start_code = None
+    if opt.fixed_code:
+        start_code = torch.randn([opt.C, opt.H // opt.f, opt.W // opt.f], device=device).unsqueeze(0).repeat(opt.n_samples, 1, 1, 1)
+    writer = None if opt.skip_save else PngWriter()
+    n_done = 0
+    with torch.no_grad(), model.ema_scope():
+        for frames, ids in loader:          # (the iterator draws its base seed from the CPU generator, as the staged loader's does)
+            test_batch, kw, state = vs.prepare(frames, ids)
+            if opt.Start_from_target:
+                start_code = runner.start_from_target(test_batch)
+            B = test_batch.shape[0]
+            x_img, _ = runner.run_batch(test_batch, kw, ref1.repeat(B, 1, 1, 1), start_code=start_code)
+            pasted, swapped = vs.paste(x_img, state)
+            n_done += B
+            if writer is None:
+                continue
+            for sid, frame in zip(ids, pasted):
+                writer.submit(os.path.join(results, sid + ".png"), frame.cpu().numpy())
+            if keep:
+                for sid, i, crop, lab, mo in zip(ids, state["index"], state["crops"].cpu().numpy(), state["labels"].cpu().numpy(), swapped.cpu().numpy()):
+                    writer.submit(os.path.join(keep["crops"], f"{i}.png"), crop)
+                    writer.submit(os.path.join(keep["masks"], f"{i}.png"), lab)
+                    writer.submit(os.path.join(keep["model_outputs"], sid + ".png"), mo)
+    torch.cuda.synchronize()
+    n_files = writer.close() if writer is not None else 0
+    n_pasted = n_files // 4 if keep else n_files
+    left = len(paths) - n_done
+    print(f"inference_swap_video --stream: {n_done} of {len(paths)} frames swapped and pasted on the device"
+          + (f" ({left} trailing frames are not swapped: drop_last)" if left else "") + f"; {n_pasted} pasted frames written to {results}, inverse "
+          f"transforms of all {len(paths)} frames to {sp['inv_transforms']}; "
+          + (f"crops, label maps and swapped crops of the swapped frames kept in {', '.join(keep.values())}" if keep else
+             "no crops, label maps or model_outputs files were written (--stream_keep writes them)")
+          + " (the mp4 + audio mux of the reference's stage 3 is not built).")
+    return n_done
+
+
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     print(opt)
+    if opt.stream or opt.stream_keep:
+        opt.stream = True
+        return run_stream(opt)
     aligned = check_align_inputs(opt) if opt.align else None
     if aligned is not None:
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -212,24 +322,7 @@ def main(argv=None):
                          "--src_image, inference_swap_video.py:430-500) is outside this build's scope; prepare\n  " + "\n  ".join(missing) +
                          "\n(the reference's stage 1 writes exactly these paths).")
     config = rcfg.load(opt.config)
-    if opt.clip_vision_config:
-        import json
-        config.model.params.cond_stage_config["params"] = {"vision_config": json.loads(opt.clip_vision_config)}
-    model = load_model_from_config(config, opt.ckpt)
-    device = torch.device("cuda")
-    if opt.precision in ("autocast", "bf16"):
-        model.set_compute_dtype(torch.bfloat16, encoders=True)
-    elif opt.precision == "fp16":                   # the bf16 mode's UNet kernels on fp16 storage / MFMA (same speed, ~17 dB closer to the exact-fp32 image);
-        model.set_compute_dtype(torch.float16)      # the towers and the VAE encoder stay fp32: this mode is chosen for its distance to "full"
-    elif opt.precision == "fp8":
-        model.set_compute_dtype("fp8", encoders=True)
-    elif opt.precision == "fullx3":                 # the fast form of "full": fp32 storage, split-bf16 GEMM operands (3 bf16 MFMA passes)
-        model.set_compute_dtype("f32x3")
-    if opt.plms:
-        from ldm.models.diffusion.plms import PLMSSampler
-        sampler = PLMSSampler(model)
-    else:
-        sampler = DDIMSampler(model)
+    model, sampler, device = load_model_and_sampler(opt, config)
     from PIL import Image
     from reface_amd.data import VideoDataset, load_source_reference
     from reface_amd.pipeline import SwapRunner
