@@ -467,6 +467,27 @@ int rf_resample_u8(const void* x_u8, int B, int H, int W, int C, const int* xbou
 int rf_video_prep_u8(const void* crops_u8, int B, int Hc, int Wc, int C, const void* labels_u8, const void* lut256_u8, const int* xbounds,
                      const int* xk, int xksize, const int* ybounds, const int* yk, int yksize, float* target, float* mask, float* inpaint, int h, int w,
                      void* stream);
+/*
+ * The identity metric of the evaluation (eval_tool/ID_retrieval/ID_retrieval.py of the reference: ArcFace ID retrieval and ID similarity of the
+ * swapped results against their sources), the two passes around the ArcFace engine:
+ *   rf_id_prep_u8  : images u8 [B, H, W, 3] (image b at images + b * image_stride bytes), labels u8 [B, Hl, Wl] (label_stride likewise) and
+ *                    lut256 u8 [256] (non-zero = a preserved label) -> out fp32 [B, 3, S, S] = ((resized / 255 - 0.5) / 0.5) * mask: the image
+ *                    through cv2's u8 INTER_LINEAR (the arithmetic of rf_resize_u8_linear: A.Resize(S, S)), the 0 / 1 preserved-label mask
+ *                    through torchvision's tensor Resize (bilinear, align_corners = False, no antialiasing, fp32, the x lerps first).  One
+ *                    pass: neither the resized image nor the mask is written (:189-228).  One size per call; callers group by size.
+ *   rf_id_retrieve : f_res fp32 [M, D], f_src fp32 [N, D] (D a multiple of 64, at most 1024), labels i32 [M] in [0, N) -> per result row, over
+ *                    the scores S[j] = sum_k f_res[r, k] f_src[j, k] (fp32 widened, fp64 products and sums, k ascending) ordered by score
+ *                    descending with TIES TO THE LOWER INDEX: top5 i32 [M, 5] = the five best source indices, best first (-1 where N < 5;
+ *                    top5[r][0] is the top-1), rank i32 [M] = the 0-based position of labels[r] in that order, sim fp64 [M] = the cosine of
+ *                    f_res[r] and f_src[labels[r]], both renormalised in fp64; then totals fp64 [4] = (rows with rank 0, rows with rank < 5,
+ *                    sum of sim, M) in a fixed summation order.  The M x N score matrix is never written (:362-390).  A label outside
+ *                    [0, N) gets rank N and similarity 0.  Rows are expected to be non-zero (the engine's are unit-norm): a zero f_res row or
+ *                    label row divides by a zero norm, as the reference does -- its sim is NaN and so is totals[2].
+ */
+int rf_id_prep_u8(const void* images_u8, int B, int H, int W, int64_t image_stride, const void* labels_u8, int Hl, int Wl, int64_t label_stride,
+                  const void* lut256_u8, float* out, int S, void* stream);
+int rf_id_retrieve(const float* f_res, int M, const float* f_src, int N, int D, const int* labels, int* top5, int* rank, double* sim, double* totals,
+                   void* stream);
 /* elementwise y = silu(x) on fp32 (emb path, openaimodel.py:219) */
 int rf_silu_f32(const float* x, float* y, int64_t n, void* stream);
 

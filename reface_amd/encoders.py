@@ -79,6 +79,10 @@ class _ArcFaceEngine:
         x = torch.zeros((B, 112, 112, self.CP), dtype=self.dt, device=dev)
         self.launches.append(ops.adaptive_avgpool(p256, x, crop=(35, 32, 188, 188), nhwc=True, name="face_pool_2"))
         self.x112 = x
+        # the evaluation's entry (eval_tool/ID_retrieval/ID_retrieval.py:124-135, clip_img=False): an already (x - 0.5) / 0.5 normalised 112x112
+        # image goes through the same pool 256 -> crop -> pool 112, without the CLIP constants.  Its own first launch; the rest is shared.
+        self.x_id = torch.empty((B, 3, 112, 112), dtype=F32, device=dev)
+        self.id_pool_1 = ops.adaptive_avgpool(self.x_id, p256, name="id_face_pool_1")
         self.body_from = len(self.launches)
         x = self._conv(x, "input_layer.0.weight", 64, bn="input_layer.1", prelu="input_layer.2.weight", cin_pad=self.CP)
         for i, (cin, depth, stride) in enumerate(arcface_units()):
@@ -165,6 +169,22 @@ class Backbone(nn.Module):
         eng = self._engine(ref224.shape[0])
         eng.x_in.copy_(ref224.to(F32))
         ops.run(eng.launches)
+        return [eng.out.clone()]
+
+    def id_input(self, B):
+        """The [B, 3, 112, 112] fp32 input buffer of ``forward_id112`` for batch B (a producer kernel may write it in place)."""
+        return self._engine(B).x_id
+
+    @torch.no_grad()
+    def forward_id112(self, x112):
+        """``IDLoss.extract_feats(x, clip_img=False)`` of the evaluation (eval_tool/ID_retrieval/ID_retrieval.py:124-135) on a [B, 3, 112, 112]
+        image normalised to [-1, 1]: pool 256 -> crop [35:223, 32:220] -> pool 112 -> body.  Passing ``id_input(B)`` itself skips the copy."""
+        eng = self._engine(x112.shape[0])
+        assert tuple(x112.shape[1:]) == (3, 112, 112), tuple(x112.shape)
+        if x112.data_ptr() != eng.x_id.data_ptr():
+            eng.x_id.copy_(x112.to(F32))
+        eng.id_pool_1()
+        ops.run(eng.launches[1:])
         return [eng.out.clone()]
 
 

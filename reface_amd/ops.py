@@ -992,6 +992,39 @@ def video_prep_u8(crops_u8, labels_u8, lut256, xtaps, ytaps, target, mask, inpai
                                          _p(target), _p(mask), _p(inpaint), h, w), (crops_u8, labels_u8, lut256, xb, xk, yb, yk, target, mask, inpaint), name)
 
 
+def id_prep_u8(images_u8, labels_u8, lut256, out, name="id_prep_u8"):
+    """The identity metric's item preparation in one launch (rf_id_prep_u8): images uint8 [B, H, W, 3] (packed images, any image stride) and
+    their label maps uint8 [B, Hl, Wl] -> out fp32 [B, 3, S, S] = ((cv2-resized / 255 - 0.5) / 0.5) * bilinear(lut256[labels] != 0)."""
+    lib = _lib.load()
+    _require_gpu(images_u8, labels_u8, lut256, out)
+    B, H, W_, C3 = images_u8.shape
+    Bl, Hl, Wl = labels_u8.shape
+    S = out.shape[2]
+    assert images_u8.dtype == labels_u8.dtype == lut256.dtype == torch.uint8 and C3 == 3 and Bl == B
+    assert images_u8.stride(3) == 1 and images_u8.stride(2) == 3 and images_u8.stride(1) == W_ * 3
+    assert labels_u8.stride(2) == 1 and labels_u8.stride(1) == Wl
+    assert lut256.is_contiguous() and lut256.numel() == 256
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B, 3, S, S), tuple(out.shape)
+    return Launch(lib.rf_id_prep_u8, (_p(images_u8), B, H, W_, images_u8.stride(0) if B > 1 else H * W_ * 3, _p(labels_u8), Hl, Wl,
+                                      labels_u8.stride(0) if B > 1 else Hl * Wl, _p(lut256), _p(out), S), (images_u8, labels_u8, lut256, out), name)
+
+
+def id_retrieve(f_res, f_src, labels, top5, rank, sim, totals, name="id_retrieve"):
+    """ID retrieval of result features f_res fp32 [M, D] against source features f_src fp32 [N, D] with labels int32 [M] (rf_id_retrieve):
+    top5 int32 [M, 5] (best first), rank int32 [M] (0-based position of the label; ties to the lower index), sim fp64 [M] (renormalised
+    cosine to f_src[label]), totals fp64 [4] = (top-1 hits, top-5 hits, sum of sim, M).  fp64 scores; no M x N matrix is written."""
+    lib = _lib.load()
+    _require_gpu(f_res, f_src, labels, top5, rank, sim, totals)
+    M, D = f_res.shape
+    N = f_src.shape[0]
+    assert f_res.dtype == f_src.dtype == torch.float32 and f_res.is_contiguous() and f_src.is_contiguous() and f_src.shape[1] == D
+    assert labels.dtype == top5.dtype == rank.dtype == torch.int32 and labels.is_contiguous() and labels.shape == (M,)
+    assert top5.is_contiguous() and top5.shape == (M, 5) and rank.is_contiguous() and rank.shape == (M,)
+    assert sim.dtype == totals.dtype == torch.float64 and sim.is_contiguous() and sim.shape == (M,) and totals.is_contiguous() and totals.shape == (4,)
+    return Launch(lib.rf_id_retrieve, (_p(f_res), M, _p(f_src), N, D, _p(labels), _p(top5), _p(rank), _p(sim), _p(totals)),
+                  (f_res, f_src, labels, top5, rank, sim, totals), name)
+
+
 def label_mask(labels_u8, lut256, out, *, invert, name="label_mask"):
     lib = _lib.load()
     _require_gpu(labels_u8, lut256, out)

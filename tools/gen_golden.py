@@ -8,7 +8,7 @@ as small ``.npz`` fixtures under tests/golden/.  Only DATA is stored (tensors + 
 needed to regenerate the weights); no reference source is copied.
 
 Usage:  python tools/gen_golden.py [group ...]     (groups: schedule unet_ops unet_small unet_full
-                                                    ddim vae arcface clip e2e bisenet align)
+                                                    ddim vae arcface clip e2e bisenet align idscore)
 """
 import os
 import sys
@@ -642,9 +642,128 @@ def gen_align():
     save("align", **out)
 
 
+def gen_idscore():
+    """The identity metric (eval_tool/ID_retrieval/ID_retrieval.py): the reference's own MaskedImagePathDataset, IDLoss.extract_feats and
+    calculate_id_given_paths on the seeded PNG folders of tests/idscore_inputs.py, ArcFace with the seeded weights (as gen_arcface).  The
+    packages that file imports and this container lacks are stubbed: natsort (reface_amd.idscore.natural_key), albumentations' Resize and
+    cv2 (imread / cvtColor over PIL on PNG inputs -- lossless, so the bytes are cv2's; A.Resize = cv2.resize INTER_LINEAR is RESTATED by
+    reface_amd.data.resize_u8_linear, not run: cv2 is absent here, see README) and the torchvision transforms it uses (ToTensor,
+    Normalize, Compose, Resize on a tensor = bilinear, align_corners=False, no antialias: torchvision 0.12).  Stored: the prepared tensors of
+    a few images, all features, labels, top-1 / top-5 / mean / similarities, the label's rank per result and the boundary gaps (the score
+    distance of the label to the nearest score across the rank 1|2 and 5|6 boundaries); a fixture whose smallest gap is below 1e-2 is
+    refused, so that exact top-k agreement can be asked of every implementation."""
+    import importlib
+    import importlib.util
+    import tempfile
+    import types
+    import PIL.Image
+    import torch.nn.functional as F
+    sys.path.insert(1, os.path.join(os.path.dirname(HERE), "tests"))
+    import idscore_inputs as I
+    from reface_amd import idscore as S
+    from reface_amd.data import resize_u8_linear
+
+    cv2 = ref_shims._mod("cv2")
+    cv2.COLOR_BGR2RGB = 4
+    cv2.imread = lambda path: np.asarray(PIL.Image.open(path).convert("RGB"), dtype=np.uint8)[:, :, ::-1].copy()
+    cv2.cvtColor = lambda img, code: img[:, :, ::-1].copy()
+    alb = ref_shims._mod("albumentations")
+    alb.Resize = lambda height, width: (lambda image: resize_u8_linear(image, height, width))
+    alb.Compose = lambda ts: (lambda image: {"image": ts[0](image)})
+    ns = ref_shims._mod("natsort")
+    ns.natsorted = lambda seq: sorted(seq, key=lambda f: S.natural_key(str(f)))
+    for name in ("tqdm", "scipy"):
+        try:
+            importlib.import_module(name)
+        except ImportError:
+            m = ref_shims._mod(name)
+            m.tqdm = lambda it, **k: it
+            m.linalg = None
+    tvt = sys.modules["torchvision.transforms"]
+
+    class ToTensor:
+        def __call__(self, img):
+            a = np.asarray(img, dtype=np.uint8)
+            a = a[:, :, None] if a.ndim == 2 else a
+            return torch.from_numpy(a.transpose(2, 0, 1).copy()).to(torch.float32).div(255)
+
+    class Normalize:
+        def __init__(self, mean, std):
+            self.mean, self.std = mean, std
+
+        def __call__(self, t):
+            return sys.modules["torchvision.transforms.functional"].normalize(t, self.mean, self.std)
+
+    class Compose:
+        def __init__(self, ts):
+            self.ts = ts
+
+        def __call__(self, x):
+            for t in self.ts:
+                x = t(x)
+            return x
+
+    class Resize:
+        def __init__(self, size, *a, **k):
+            self.size = tuple(size)
+
+        def __call__(self, t):
+            assert torch.is_tensor(t) and t.dim() == 3
+            return F.interpolate(t[None], size=self.size, mode="bilinear", align_corners=False, antialias=False)[0]
+
+    tvt.ToTensor, tvt.Normalize, tvt.Compose, tvt.Resize = ToTensor, Normalize, Compose, Resize
+    sys.modules["torchvision"].transforms = tvt
+    # by path: `eval_tool` is a stub module in ref_shims and a package of this repository; neither is the reference's
+    spec = importlib.util.spec_from_file_location("ref_id_retrieval", "/root/reference/eval_tool/ID_retrieval/ID_retrieval.py")
+    R = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(R)
+
+    net = R.Backbone(input_size=112, num_layers=50, drop_ratio=0.6, mode="ir_se").eval()
+    load_strict(net, P.seeded_state_dict(P.arcface_param_specs(), S.ARCFACE_TEST_SEED))
+    idl = R.IDLoss.__new__(R.IDLoss)
+    torch.nn.Module.__init__(idl)
+    idl.multiscale = True
+    idl.face_pool_1 = torch.nn.AdaptiveAvgPool2d((256, 256))
+    idl.face_pool_2 = torch.nn.AdaptiveAvgPool2d((112, 112))
+    idl.facenet = net
+    idl.eval()
+    idl.cuda = lambda: idl
+    R.IDLoss = lambda: idl
+
+    data = I.build()
+    with tempfile.TemporaryDirectory() as tmp:
+        paths = I.write_folders(tmp, data)
+        lists = [R.natsorted([os.path.join(p, n) for n in os.listdir(p)]) for p in paths]
+        assert [os.path.basename(f) for f in lists[0]] == data["src_names"] and [os.path.basename(f) for f in lists[1]] == data["res_names"]
+        ds_src = R.MaskedImagePathDataset(lists[0], maskfiles=lists[2], data_name=I.DATASET)
+        ds_res = R.MaskedImagePathDataset(lists[1], maskfiles=lists[3], data_name=I.DATASET)
+        x_src = torch.cat([ds_src[i] for i in range(len(ds_src))])
+        x_res = torch.cat([ds_res[i] for i in range(len(ds_res))])
+        f_src = idl.extract_feats(x_src)[-1]
+        f_res = idl.extract_feats(x_res)[-1]
+        args = types.SimpleNamespace(arcface=True)
+        top1, top5, mean, sims = R.calculate_id_given_paths(paths, 16, torch.device("cpu"), 2048, 0, data_name=I.DATASET, args=args)
+        ds_all = R.MaskedImagePathDataset(lists[0], maskfiles=lists[2], data_name="other")          # every label kept: the image resize alone
+        x_nomask = torch.cat([ds_all[i] for i in I.PREP_SAMPLES["src"]])
+    labels = data["labels"]
+    h = S.score_host(f_src.numpy(), f_res.numpy(), labels)
+    assert h["top1"] == top1 and h["top5"] == top5, (h["top1"], top1, h["top5"], top5)
+    assert np.abs(h["similarities"] - sims).max() < 1e-12 and abs(h["mean"] - mean) < 1e-12
+    gaps = S.boundary_gaps(f_src.numpy(), f_res.numpy(), labels)
+    print(f"  top1 {top1:.4f}  top5 {top5:.4f}  mean {mean:.4f}  ranks {h['rank'].tolist()}")
+    print(f"  similarities {np.round(sims, 3).tolist()}")
+    print(f"  smallest boundary gap {gaps.min():.4f}")
+    if gaps.min() < 1e-2:
+        raise SystemExit(f"gen_idscore: smallest boundary gap {gaps.min():.3e} < 1e-2: not a fixture for exact top-k checks; change the seeds")
+    assert 0.0 < top1 < top5 < 1.0, "the fixture must leave both accuracies non-trivial"
+    save("idscore", prep_src=x_src[I.PREP_SAMPLES["src"]], prep_res=x_res[I.PREP_SAMPLES["res"]], prep_src_nomask=x_nomask,
+         f_src=f_src, f_res=f_res, labels=labels, top1=np.float64(top1), top5=np.float64(top5), mean=np.float64(mean),
+         similarities=np.asarray(sims, dtype=np.float64), rank=h["rank"], pred=h["pred"], gaps=gaps, seed=S.ARCFACE_TEST_SEED)
+
+
 GROUPS = dict(ddim_full=gen_ddim_full, unet_keys=gen_unet_keys, plms=gen_plms, schedule=gen_schedule, unet_ops=gen_unet_ops, unet_small=gen_unet_small, unet_full=gen_unet_full,
               ddim=gen_ddim, vae=gen_vae, arcface=gen_arcface, clip=gen_clip, e2e=gen_e2e,
-              bisenet=gen_bisenet, align=gen_align)
+              bisenet=gen_bisenet, align=gen_align, idscore=gen_idscore)
 
 if __name__ == "__main__":
     sel = sys.argv[1:] or [g for g in GROUPS if g != "ddim_full"]          # (ddim_full: 20 minutes; ask for it by name)
