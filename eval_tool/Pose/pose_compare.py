@@ -1,0 +1,66 @@
+#!/usr/bin/env python3
+"""Pose score of a swap run on the MI355X-native engines: the mean L2 distance between the Hopenet head-pose angles (yaw, pitch, roll, in
+degrees) of the swapped results and those of their targets -- the reference's eval_tool/Pose/pose_compare.py, same positionals, options
+and printed lines:
+
+    python eval_tool/Pose/pose_compare.py --device cuda <target images> <results>
+
+Both folders are listed in natural order of the file names.  The label of a result is the LAST number in its file name minus the smallest
+one of its folder, and it is a position in the sorted target list: that target's angles are the ones the result is compared with.
+Everything after the decode runs on the GPU (reface_amd/posescore.py: rf_pose_prep_u8, the ResNet-50 engine, rf_pose_head,
+rf_pose_distance).  ``.npz`` paths are refused: the reference's branch for them cannot run.
+
+Additions (not in the reference): ``--hopenet_ckpt`` (``none`` = the seeded weights of the tests), ``--json FILE``.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def build_parser():
+    from reface_amd.posescore import DEFAULT_HOPENET_CKPT
+    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("--batch-size", type=int, default=20, help="images per Hopenet engine run")
+    p.add_argument("--num-workers", type=int, help="decode workers of the loader (default: the CPUs this process may run on, 8 at the most)")
+    p.add_argument("--device", type=str, default=None, help="cuda or cuda:<i>; the HIP kernels have no CPU path")
+    p.add_argument("path", type=str, nargs=2, default=["dataset/FaceData/CelebAMask-HQ/CelebA-HQ-img", "results/test_bench/results"],
+                   help="target images, results")
+    # ---- additions
+    p.add_argument("--hopenet_ckpt", type=str, default=DEFAULT_HOPENET_CKPT, help="(addition) Hopenet weights; 'none' = the seeded weights the tests use")
+    p.add_argument("--json", type=str, default=None,
+                   help="(addition) write Pose_value, distances, labels, degrees, image count and images/s (decode to score; engine construction excluded) to this file")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    import torch
+    from reface_amd.posescore import PoseScorer, load_hopenet_state
+    device = torch.device(args.device if args.device is not None else "cuda")
+    if device.type != "cuda":
+        raise SystemExit(f"pose_compare: --device {args.device}: the HIP kernels run on the GPU only (there is no CPU fallback)")
+    num_workers = min(len(os.sched_getaffinity(0)), 8) if args.num_workers is None else args.num_workers
+    for p in args.path:
+        if not os.path.exists(p):
+            raise RuntimeError("Invalid path: %s" % p)
+        if p.endswith(".npz"):
+            raise SystemExit(f"pose_compare: {p}: .npz statistics are not supported (the reference's .npz branch cannot run)")
+    print("Loading hopenet")
+    scorer = PoseScorer(load_hopenet_state(args.hopenet_ckpt), batch=args.batch_size, device=device)
+    r = scorer.score_folders(args.path, num_workers=num_workers)
+    print("Pose_value: ", r["pose_value"])
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump({"pose_value": r["pose_value"], "distances": [float(d) for d in r["distances"]], "labels": r["labels"],
+                       "degrees_target": r["degrees_target"].tolist(), "degrees_result": r["degrees_result"].tolist(), "images": r["images"],
+                       "images_per_s": r["images_per_s"], "seconds": r["seconds"]}, f)
+    return r
+
+
+if __name__ == "__main__":
+    main()

@@ -488,6 +488,28 @@ int rf_id_prep_u8(const void* images_u8, int B, int H, int W, int64_t image_stri
                   const void* lut256_u8, float* out, int S, void* stream);
 int rf_id_retrieve(const float* f_res, int M, const float* f_src, int N, int D, const int* labels, int* top5, int* rank, double* sim, double* totals,
                    void* stream);
+/*
+ * The pose metric of the evaluation (eval_tool/Pose/pose_compare.py of the reference: Hopenet head-pose angles of the swapped results against
+ * those of their targets), the three passes around the ResNet-50 body (which runs on rf_conv_gemm):
+ *   rf_pose_prep_u8  : images u8 [B, H, W, 3] (image b at images + b * image_stride bytes; any H, W >= 1) -> out fp32 NHWC [B, 224, 224, 8]
+ *                      (16-byte aligned) = (resize(u8 / 255) - mean) / std with the ImageNet constants in channels 0..2, zeros in 3..7 (the
+ *                      7x7 stem's cin_pad = 8 layout).  The resize is torchvision's tensor Resize of 0.12: bilinear, align_corners = False,
+ *                      no antialiasing at any size, fp32, src = max((dst + 0.5) * (in / out) - 0.5, 0), the upper tap clamped to the last
+ *                      pixel, the x lerps first; the coordinate and both lerps are FMAs, as in PyTorch's CPU build, where the reference
+ *                      resizes.  One pass, one size per call; callers group by size (:91-99).
+ *   rf_pose_head     : feat fp32 [B, 7, 7, 2048] (layer4, NHWC), w198 fp32 [198, 2048] (fc_yaw | fc_pitch | fc_roll stacked on rows, 16-byte
+ *                      aligned), b198 fp32 [198] -> degrees fp32 [B, 3] (yaw, pitch, roll) and, when `logits` is not null, logits fp32
+ *                      [B, 198].  Per image: the mean of the 49 pixels, the 198 dot products, per 66-bin head a softmax shifted by the head's
+ *                      maximum (finite for any finite logits) and degrees = sum(p * [0..65]) * 3 - 99 (:101-108).  One workgroup per image:
+ *                      the summation order, hence every bit of an image's outputs, does not depend on B.
+ *   rf_pose_distance : deg_res fp32 [M, 3], deg_tgt fp32 [N, 3], labels i32 [M] in [0, N) -> dist fp64 [M] = the L2 norm of
+ *                      (double)deg_tgt[labels[r]] - (double)deg_res[r] (widened before the subtraction, squares summed in index order), then
+ *                      totals fp64 [2] = (sum of dist, M) in a fixed summation order: equal bits on every run (:320-323).  A label outside
+ *                      [0, N) is not dereferenced: its dist is NaN, and so is totals[0]; callers refuse such labels before the launch.
+ */
+int rf_pose_prep_u8(const void* images_u8, int B, int H, int W, int64_t image_stride, float* out, void* stream);
+int rf_pose_head(const float* feat, int B, const float* w198, const float* b198, float* degrees, float* logits, void* stream);
+int rf_pose_distance(const float* deg_res, int M, const float* deg_tgt, int N, const int* labels, double* dist, double* totals, void* stream);
 /* elementwise y = silu(x) on fp32 (emb path, openaimodel.py:219) */
 int rf_silu_f32(const float* x, float* y, int64_t n, void* stream);
 

@@ -1025,6 +1025,44 @@ def id_retrieve(f_res, f_src, labels, top5, rank, sim, totals, name="id_retrieve
                   (f_res, f_src, labels, top5, rank, sim, totals), name)
 
 
+def pose_prep_u8(images_u8, out, name="pose_prep_u8"):
+    """The pose metric's item preparation in one launch (rf_pose_prep_u8): images uint8 [B, H, W, 3] (packed images, any image stride, any
+    H, W >= 1) -> out fp32 NHWC [B, 224, 224, 8] = (bilinear(u8 / 255) - mean) / std in channels 0..2, zeros in 3..7."""
+    lib = _lib.load()
+    _require_gpu(images_u8, out)
+    B, H, W_, C3 = images_u8.shape
+    assert images_u8.dtype == torch.uint8 and C3 == 3
+    assert images_u8.stride(3) == 1 and images_u8.stride(2) == 3 and images_u8.stride(1) == W_ * 3
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B, 224, 224, 8), tuple(out.shape)
+    return Launch(lib.rf_pose_prep_u8, (_p(images_u8), B, H, W_, images_u8.stride(0) if B > 1 else H * W_ * 3, _p(out)), (images_u8, out), name)
+
+
+def pose_head(feat, w198, b198, degrees, logits=None, name="pose_head"):
+    """Hopenet's head (rf_pose_head): layer4 features fp32 [B, 7, 7, 2048], the stacked fc_yaw | fc_pitch | fc_roll weights [198, 2048] and
+    bias [198] -> degrees fp32 [B, 3]; logits fp32 [B, 198] when given.  One workgroup per image: the result does not depend on B."""
+    lib = _lib.load()
+    _require_gpu(feat, w198, b198, degrees, logits)
+    B = feat.shape[0]
+    assert feat.dtype == w198.dtype == b198.dtype == degrees.dtype == torch.float32
+    assert feat.shape == (B, 7, 7, 2048) and feat.is_contiguous() and w198.shape == (198, 2048) and w198.is_contiguous()
+    assert b198.shape == (198,) and b198.is_contiguous() and degrees.shape == (B, 3) and degrees.is_contiguous()
+    assert logits is None or (logits.dtype == torch.float32 and logits.shape == (B, 198) and logits.is_contiguous())
+    return Launch(lib.rf_pose_head, (_p(feat), B, _p(w198), _p(b198), _p(degrees), _p(logits)), (feat, w198, b198, degrees, logits), name)
+
+
+def pose_distance(deg_res, deg_tgt, labels, dist, totals, name="pose_distance"):
+    """L2 distances of result degrees fp32 [M, 3] to target degrees fp32 [N, 3] picked by labels int32 [M] (rf_pose_distance): dist fp64
+    [M], totals fp64 [2] = (sum of dist, M), in fp64 and in a fixed summation order.  The labels must lie in [0, N): the caller checks."""
+    lib = _lib.load()
+    _require_gpu(deg_res, deg_tgt, labels, dist, totals)
+    M, N = deg_res.shape[0], deg_tgt.shape[0]
+    assert deg_res.dtype == deg_tgt.dtype == torch.float32 and deg_res.shape == (M, 3) and deg_tgt.shape == (N, 3)
+    assert deg_res.is_contiguous() and deg_tgt.is_contiguous()
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.shape == (M,)
+    assert dist.dtype == totals.dtype == torch.float64 and dist.is_contiguous() and dist.shape == (M,) and totals.is_contiguous() and totals.shape == (2,)
+    return Launch(lib.rf_pose_distance, (_p(deg_res), M, _p(deg_tgt), N, _p(labels), _p(dist), _p(totals)), (deg_res, deg_tgt, labels, dist, totals), name)
+
+
 def label_mask(labels_u8, lut256, out, *, invert, name="label_mask"):
     lib = _lib.load()
     _require_gpu(labels_u8, lut256, out)

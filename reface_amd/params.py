@@ -436,6 +436,41 @@ def bisenet_param_specs(n_classes=19):
     return s
 
 
+def hopenet_units():
+    """(prefix, cin, planes, stride) of the sixteen Bottlenecks of Hopenet's ResNet-50 (hopenet.py:18-21, 38-53: layers [3, 4, 6, 3]); a
+    block maps cin -> 4 * planes channels, its stride sits on the 3x3 conv2."""
+    units, cin = [], 64
+    for li, (planes, n, stride) in enumerate(((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2)), start=1):
+        for i in range(n):
+            units.append((f"layer{li}.{i}", cin, planes, stride if i == 0 else 1))
+            cin = planes * 4
+    return units
+
+
+def hopenet_param_specs(num_bins=66):
+    """State-dict keys of ``Hopenet(Bottleneck, [3, 4, 6, 3], 66)`` (eval_tool/face_vid2vid/modules/hopenet.py:10-28 over torchvision's
+    Bottleneck), in module order: 326 entries, the vestigial ``fc_finetune`` (in the checkpoint, never computed) included."""
+    s = OrderedDict()
+    s["conv1.weight"] = (64, 3, 7, 7)
+    _bn(s, "bn1", 64)
+    for p, cin, planes, stride in hopenet_units():
+        s[f"{p}.conv1.weight"] = (planes, cin, 1, 1)
+        _bn(s, f"{p}.bn1", planes)
+        s[f"{p}.conv2.weight"] = (planes, planes, 3, 3)
+        _bn(s, f"{p}.bn2", planes)
+        s[f"{p}.conv3.weight"] = (planes * 4, planes, 1, 1)
+        _bn(s, f"{p}.bn3", planes * 4)
+        if stride != 1 or cin != planes * 4:
+            s[f"{p}.downsample.0.weight"] = (planes * 4, cin, 1, 1)
+            _bn(s, f"{p}.downsample.1", planes * 4)
+    for head in ("fc_yaw", "fc_pitch", "fc_roll"):
+        s[f"{head}.weight"] = (num_bins, 2048)
+        s[f"{head}.bias"] = (num_bins,)
+    s["fc_finetune.weight"] = (3, 2048 + 3)
+    s["fc_finetune.bias"] = (3,)
+    return s
+
+
 def cond_head_specs():
     """Top-level LatentDiffusion conditioning heads (ddpm.py:698-733)."""
     s = OrderedDict()

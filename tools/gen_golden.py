@@ -8,7 +8,7 @@ as small ``.npz`` fixtures under tests/golden/.  Only DATA is stored (tensors + 
 needed to regenerate the weights); no reference source is copied.
 
 Usage:  python tools/gen_golden.py [group ...]     (groups: schedule unet_ops unet_small unet_full
-                                                    ddim vae arcface clip e2e bisenet align idscore)
+                                                    ddim vae arcface clip e2e bisenet align idscore pose)
 """
 import os
 import sys
@@ -642,6 +642,46 @@ def gen_align():
     save("align", **out)
 
 
+def _install_tv_transforms():
+    """torchvision.transforms' ToTensor, Normalize, Compose and Resize (on a tensor: bilinear, align_corners=False, no antialias at any size --
+    torchvision 0.12) restated on the stub ``torchvision`` of tools/ref_shims.py, for the evaluation tools of the reference."""
+    import torch.nn.functional as F
+    tvt = sys.modules["torchvision.transforms"]
+
+    class ToTensor:
+        def __call__(self, img):
+            a = np.asarray(img, dtype=np.uint8)
+            a = a[:, :, None] if a.ndim == 2 else a
+            return torch.from_numpy(a.transpose(2, 0, 1).copy()).to(torch.float32).div(255)
+
+    class Normalize:
+        def __init__(self, mean, std):
+            self.mean, self.std = mean, std
+
+        def __call__(self, t):
+            return sys.modules["torchvision.transforms.functional"].normalize(t, self.mean, self.std)
+
+    class Compose:
+        def __init__(self, ts):
+            self.ts = ts
+
+        def __call__(self, x):
+            for t in self.ts:
+                x = t(x)
+            return x
+
+    class Resize:
+        def __init__(self, size, *a, **k):
+            self.size = tuple(size)
+
+        def __call__(self, t):
+            assert torch.is_tensor(t) and t.dim() == 3
+            return F.interpolate(t[None], size=self.size, mode="bilinear", align_corners=False, antialias=False)[0]
+
+    tvt.ToTensor, tvt.Normalize, tvt.Compose, tvt.Resize = ToTensor, Normalize, Compose, Resize
+    sys.modules["torchvision"].transforms = tvt
+
+
 def gen_idscore():
     """The identity metric (eval_tool/ID_retrieval/ID_retrieval.py): the reference's own MaskedImagePathDataset, IDLoss.extract_feats and
     calculate_id_given_paths on the seeded PNG folders of tests/idscore_inputs.py, ArcFace with the seeded weights (as gen_arcface).  The
@@ -679,40 +719,7 @@ def gen_idscore():
             m = ref_shims._mod(name)
             m.tqdm = lambda it, **k: it
             m.linalg = None
-    tvt = sys.modules["torchvision.transforms"]
-
-    class ToTensor:
-        def __call__(self, img):
-            a = np.asarray(img, dtype=np.uint8)
-            a = a[:, :, None] if a.ndim == 2 else a
-            return torch.from_numpy(a.transpose(2, 0, 1).copy()).to(torch.float32).div(255)
-
-    class Normalize:
-        def __init__(self, mean, std):
-            self.mean, self.std = mean, std
-
-        def __call__(self, t):
-            return sys.modules["torchvision.transforms.functional"].normalize(t, self.mean, self.std)
-
-    class Compose:
-        def __init__(self, ts):
-            self.ts = ts
-
-        def __call__(self, x):
-            for t in self.ts:
-                x = t(x)
-            return x
-
-    class Resize:
-        def __init__(self, size, *a, **k):
-            self.size = tuple(size)
-
-        def __call__(self, t):
-            assert torch.is_tensor(t) and t.dim() == 3
-            return F.interpolate(t[None], size=self.size, mode="bilinear", align_corners=False, antialias=False)[0]
-
-    tvt.ToTensor, tvt.Normalize, tvt.Compose, tvt.Resize = ToTensor, Normalize, Compose, Resize
-    sys.modules["torchvision"].transforms = tvt
+    _install_tv_transforms()
     # by path: `eval_tool` is a stub module in ref_shims and a package of this repository; neither is the reference's
     spec = importlib.util.spec_from_file_location("ref_id_retrieval", "/root/reference/eval_tool/ID_retrieval/ID_retrieval.py")
     R = importlib.util.module_from_spec(spec)
@@ -761,9 +768,139 @@ def gen_idscore():
          similarities=np.asarray(sims, dtype=np.float64), rank=h["rank"], pred=h["pred"], gaps=gaps, seed=S.ARCFACE_TEST_SEED)
 
 
+def _tv_bottleneck():
+    """torchvision 0.12's ``models.resnet.Bottleneck`` restated (torchvision is absent here, see README): 1x1 -> 3x3 -> 1x1 convolutions
+    without bias, each followed by BatchNorm, ReLU after the first two, the stride on the 3x3 ``conv2`` (the "v1.5" placement),
+    ``out = relu(bn3(conv3(.)) + identity)`` with ``identity = downsample(x)`` where a downsample is given.  Module names, hence
+    state-dict keys, are torchvision's."""
+    nn = torch.nn
+
+    class Bottleneck(nn.Module):
+        expansion = 4
+
+        def __init__(self, inplanes, planes, stride=1, downsample=None):
+            super().__init__()
+            self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=1, bias=False)
+            self.bn1 = nn.BatchNorm2d(planes)
+            self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, stride=stride, padding=1, bias=False)
+            self.bn2 = nn.BatchNorm2d(planes)
+            self.conv3 = nn.Conv2d(planes, planes * self.expansion, kernel_size=1, bias=False)
+            self.bn3 = nn.BatchNorm2d(planes * self.expansion)
+            self.relu = nn.ReLU(inplace=True)
+            self.downsample = downsample
+            self.stride = stride
+
+        def forward(self, x):
+            identity = x if self.downsample is None else self.downsample(x)
+            out = self.relu(self.bn1(self.conv1(x)))
+            out = self.relu(self.bn2(self.conv2(out)))
+            out = self.bn3(self.conv3(out))
+            return self.relu(out + identity)
+
+    return Bottleneck
+
+
+def gen_pose():
+    """The pose metric (eval_tool/Pose/pose_compare.py over eval_tool/face_vid2vid/modules/hopenet.py): the reference's own Hopenet,
+    ImagePathDataset, compute_features and calculate_id_given_paths on the seeded PNG folders of tests/pose_inputs.py, with the seeded
+    weights in place of the checkpoint file.  Both files are loaded by path.  What this container lacks is stubbed: natsort
+    (reface_amd.idscore.natural_key), the torchvision transforms (_install_tv_transforms) and torchvision.models.resnet.Bottleneck
+    (_tv_bottleneck); torch.load of the checkpoint path returns the seeded state dict.  Stored: the state-dict key layout of the reference
+    module, the labels, the prepared tensors of two images (a downscale and the upscale), the degrees of all images in fp32 (the reference
+    as it runs) and from the same module and inputs in float64, and the distances and Pose_value of both.  A degenerate fixture is refused:
+    every angle must vary by >= 0.1 degree (std) over the images, no softmax may be saturated (max <= 0.9), Pose_value >= 0.2 degree, and
+    labelling by the first number or pairing by position must each move Pose_value by more than 0.05 degree."""
+    import importlib
+    import importlib.util
+    import tempfile
+    sys.path.insert(1, os.path.join(os.path.dirname(HERE), "tests"))
+    import pose_inputs as I
+    from reface_amd import idscore as S
+    from reface_amd import posescore as PS
+
+    ns = ref_shims._mod("natsort")
+    ns.natsorted = lambda seq: sorted(seq, key=lambda f: S.natural_key(str(f)))
+    for name in ("tqdm", "scipy"):
+        try:
+            importlib.import_module(name)
+        except ImportError:
+            m = ref_shims._mod(name)
+            m.tqdm = lambda it, **k: it
+            m.linalg = None
+    _install_tv_transforms()
+    Bottleneck = _tv_bottleneck()
+    tvr = ref_shims._mod("torchvision.models.resnet")
+    tvr.Bottleneck = Bottleneck
+    sys.modules["torchvision.models"].resnet = tvr
+    # by path: `eval_tool` is a stub module in ref_shims and a package of this repository; neither is the reference's
+    spec = importlib.util.spec_from_file_location("eval_tool.face_vid2vid.modules.hopenet", "/root/reference/eval_tool/face_vid2vid/modules/hopenet.py")
+    H = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(H)
+    ref_shims._mod("eval_tool.face_vid2vid")
+    ref_shims._mod("eval_tool.face_vid2vid.modules").hopenet = H
+    sys.modules["eval_tool.face_vid2vid.modules.hopenet"] = H
+    spec = importlib.util.spec_from_file_location("ref_pose_compare", "/root/reference/eval_tool/Pose/pose_compare.py")
+    R = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(R)
+
+    net = H.Hopenet(Bottleneck, [3, 4, 6, 3], 66).eval()
+    ref_sd = net.state_dict()
+    keys = np.array(list(ref_sd.keys()))
+    shapes = np.array([",".join(str(d) for d in v.shape) for v in ref_sd.values()])
+    assert len(keys) == 326, len(keys)
+    sd = P.seeded_state_dict(P.hopenet_param_specs(), PS.SEED)
+    net.load_state_dict(sd, strict=True)
+
+    data = I.build()
+    labels = data["labels"]
+    with tempfile.TemporaryDirectory() as tmp:
+        paths = I.write_folders(tmp, data)
+        lists = [R.natsorted([os.path.join(p, n) for n in os.listdir(p)]) for p in paths]
+        assert [os.path.basename(f) for f in lists[0]] == data["tgt_names"] and [os.path.basename(f) for f in lists[1]] == data["res_names"]
+        load = torch.load
+        torch.load = lambda *a, **k: sd          # the checkpoint path of calculate_id_given_paths
+        try:
+            value = float(R.calculate_id_given_paths(paths, 20, torch.device("cpu"), 2048, 0))
+            _, ref_labels = R.compute_features_wrapp(paths[1], net, 20, 2048, torch.device("cpu"), 0)
+        finally:
+            torch.load = load
+        assert list(ref_labels) == labels.tolist(), (ref_labels, labels)
+        deg32 = [R.compute_features(files, net, 20, 2048, torch.device("cpu"), 0) for files in lists]
+        x = [torch.stack([t for t in R.ImagePathDataset(files)]) for files in lists]
+    prep = x[0][I.PREP_SAMPLES["tgt"]]
+    net64 = H.Hopenet(Bottleneck, [3, 4, 6, 3], 66).eval()
+    net64.load_state_dict(sd, strict=True)
+    net64.double()
+    deg64, pmax = [], 0.0
+    for xs in x:
+        heads = net64(xs.double())
+        pmax = max([pmax] + [float(torch.softmax(h, dim=1).max()) for h in heads])
+        deg64.append(torch.stack([R.headpose_pred_to_degree(h) for h in heads], dim=1).numpy())
+    assert deg64[0].dtype == np.float64 and deg32[0].dtype == np.float64
+
+    h32 = PS.score_host(deg32[0], deg32[1], labels)
+    h64 = PS.score_host(deg64[0], deg64[1], labels)
+    assert abs(h32["pose_value"] - value) < 1e-12, (h32["pose_value"], value)
+    e_ref = max(float(np.abs(a - b).max()) for a, b in zip(deg32, deg64))
+    std = np.concatenate(deg64).std(axis=0)
+    by_first = PS.score_host(deg64[0], deg64[1], I.first_number_labels())["pose_value"]
+    by_position = PS.score_host(deg64[0], deg64[1], list(range(len(labels))))["pose_value"]
+    print(f"  Pose_value fp32 {value:.6f}  fp64 {h64['pose_value']:.6f}  E_ref = max|deg_f32 - deg_f64| = {e_ref:.3e}")
+    print(f"  distances {np.round(h64['distances'], 3).tolist()}")
+    print(f"  per-angle std {np.round(std, 3).tolist()}  largest softmax value {pmax:.3f}")
+    print(f"  Pose_value with first-number labels {by_first:.4f}, paired by position {by_position:.4f}")
+    if std.min() < 0.1 or pmax > 0.9 or h64["pose_value"] < 0.2:
+        raise SystemExit(f"gen_pose: degenerate fixture (per-angle std {std.tolist()}, softmax max {pmax}, Pose_value {h64['pose_value']}); change the seeds")
+    assert abs(by_first - h64["pose_value"]) > 0.05 and abs(by_position - h64["pose_value"]) > 0.05, "the fixture must expose a wrong labelling and a wrong pairing"
+    save("pose", keys=keys, shapes=shapes, labels=labels, prep=prep, prep_index=np.array(I.PREP_SAMPLES["tgt"]),
+         deg_f32_tgt=deg32[0], deg_f32_res=deg32[1], deg_f64_tgt=deg64[0], deg_f64_res=deg64[1],
+         dist_f32=h32["distances"], dist_f64=h64["distances"], pose_value_f32=np.float64(value), pose_value_f64=np.float64(h64["pose_value"]),
+         e_ref=np.float64(e_ref), seed=PS.SEED)
+
+
 GROUPS = dict(ddim_full=gen_ddim_full, unet_keys=gen_unet_keys, plms=gen_plms, schedule=gen_schedule, unet_ops=gen_unet_ops, unet_small=gen_unet_small, unet_full=gen_unet_full,
               ddim=gen_ddim, vae=gen_vae, arcface=gen_arcface, clip=gen_clip, e2e=gen_e2e,
-              bisenet=gen_bisenet, align=gen_align, idscore=gen_idscore)
+              bisenet=gen_bisenet, align=gen_align, idscore=gen_idscore, pose=gen_pose)
 
 if __name__ == "__main__":
     sel = sys.argv[1:] or [g for g in GROUPS if g != "ddim_full"]          # (ddim_full: 20 minutes; ask for it by name)
