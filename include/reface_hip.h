@@ -31,9 +31,10 @@ enum { RF_F32 = 0, RF_BF16 = 1, RF_FP8_E4M3 = 2 /* OCP e4m3fn weights (rf_conv_g
        RF_BF16X3 = 3 /* split-bf16 operand pairs, see rf_conv_gemm_desc.dtype and rf_split_bf16 */,
        RF_F16 = 4 /* IEEE binary16 storage (the "fp16" throughput mode) */ };
 
-/* epilogue activations of rf_conv_gemm */
+/* epilogue activations of rf_conv_gemm.  RF_ACT_ADD_RELU is the one code applied AFTER the residual: out = relu(alpha * acc + bias + rowvec
+ * + residual), the tail of a ResNet block (never split-K; not with LayerNorm folding or fp8 output) */
 enum { RF_ACT_NONE = 0, RF_ACT_GEGLU = 1, RF_ACT_SILU = 2, RF_ACT_QUICK_GELU = 3, RF_ACT_GELU = 4,
-       RF_ACT_RELU = 5, RF_ACT_SIGMOID = 6, RF_ACT_PRELU = 7 };
+       RF_ACT_RELU = 5, RF_ACT_SIGMOID = 6, RF_ACT_PRELU = 7, RF_ACT_ADD_RELU = 8 };
 
 const char* rf_last_error(void);
 int rf_version(void);
@@ -510,6 +511,28 @@ int rf_id_retrieve(const float* f_res, int M, const float* f_src, int N, int D, 
 int rf_pose_prep_u8(const void* images_u8, int B, int H, int W, int64_t image_stride, float* out, void* stream);
 int rf_pose_head(const float* feat, int B, const float* w198, const float* b198, float* degrees, float* logits, void* stream);
 int rf_pose_distance(const float* deg_res, int M, const float* deg_tgt, int N, const int* labels, double* dist, double* totals, void* stream);
+/*
+ * The expression metric of the evaluation (eval_tool/Expression/expression_compare_face_recon.py of the reference: the 64 expression
+ * coefficients of Deep3DFaceRecon's net_recon of the swapped results against those of their targets), the three passes around the ResNet-50
+ * body (which runs on rf_conv_gemm):
+ *   rf_expr_prep_u8  : images u8 [B, H, W, 3] (image b at images + b * image_stride bytes; any H, W >= 1) and the tap tables of PIL's
+ *                      Image.resize((512, 512), BICUBIC) per axis (bounds i32 [512, 2] = first input index and tap count, taps i32
+ *                      [512, ksize], 22-bit fixed point) -> out fp32 NHWC [B, 512, 512, 8] (16-byte aligned) = resized byte / 255 in channels
+ *                      0..2, zeros in 3..7.  PIL's two integer passes with the u8 rounding between them; the horizontally resampled rows live
+ *                      in LDS only, for every source size (no intermediate in global memory).  A 512 x 512 source comes out as its own bytes.
+ *   rf_expr_head     : feat fp32 [B, P, 2048] (layer4, NHWC, P pixels per image), w fp32 [257, 2048] (final_layers.0..6 stacked on rows, 16-byte
+ *                      aligned), bias fp32 [257] -> coeffs fp32 [B, 257] = bias + w . (sum over the P pixels in ascending order / P).  One
+ *                      workgroup per image: every bit of an image's coefficients is independent of B.
+ *   rf_expr_distance : coef_res fp32 [M, ld], coef_tgt fp32 [N, ld], labels i32 [M] in [0, N) -> dist fp64 [M] = the L2 norm over columns
+ *                      [col0, col0 + ncols) of (double)coef_tgt[labels[r]] - (double)coef_res[r] (widened before the subtraction, squares
+ *                      summed in column order), then totals fp64 [2] = (sum of dist, M) in a fixed summation order.  Columns outside the range
+ *                      are not read.  A label outside [0, N) is not dereferenced: its dist is NaN; callers refuse such labels before the launch.
+ */
+int rf_expr_prep_u8(const void* images_u8, int B, int H, int W, int64_t image_stride, const int* xbounds, const int* xk, int xksize,
+                    const int* ybounds, const int* yk, int yksize, float* out, void* stream);
+int rf_expr_head(const float* feat, int B, int P, const float* w257, const float* b257, float* coeffs, void* stream);
+int rf_expr_distance(const float* coef_res, int M, const float* coef_tgt, int N, int ld, int col0, int ncols, const int* labels, double* dist,
+                     double* totals, void* stream);
 /* elementwise y = silu(x) on fp32 (emb path, openaimodel.py:219) */
 int rf_silu_f32(const float* x, float* y, int64_t n, void* stream);
 

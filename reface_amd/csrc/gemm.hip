@@ -1,6 +1,7 @@
 // Implicit-GEMM convolution / linear layer on the gfx950 matrix cores.
 //
 //   out[m, n] = act(alpha * sum_k A[m, k] W[n, k] + bias[n] + rowvec[sample(m), n]) + residual[m, n]
+//   (RF_ACT_ADD_RELU alone acts after the residual: out = relu(alpha * sum + bias + rowvec + residual), direct and staged epilogues, no split-K)
 //
 // One kernel template serves both storage types through a common *byte* geometry: a K-tile is
 // 128 bytes of K per row (64 bf16 or 32 fp32), LDS rows are 128 B with a 16-B-slot XOR swizzle,
@@ -1113,6 +1114,10 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                             } else {
 #pragma unroll
                                 for (int e = 0; e < E; ++e) v[e] = acc[i][j][h * E + e] * p.alpha + cb[(h * E + e) >> 2][(h * E + e) & 3] + (resp ? f[e] : 0.0f);
+                                if (p.act == RF_ACT_ADD_RELU) {
+#pragma unroll
+                                    for (int e = 0; e < E; ++e) v[e] = fmaxf(v[e], 0.0f);
+                                }
                             }
                             const u32x4_t w = pack16<TO>(v);
                             ((u32x4_t*)dst)[h] = w;
@@ -1368,6 +1373,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                             v[0] += rq[u][0]; v[1] += rq[u][1]; v[2] += rq[u][2]; v[3] += rq[u][3];
                         }
                     }
+                    if (p.act == RF_ACT_ADD_RELU) { v[0] = fmaxf(v[0], 0.0f); v[1] = fmaxf(v[1], 0.0f); v[2] = fmaxf(v[2], 0.0f); v[3] = fmaxf(v[3], 0.0f); }
                     if constexpr (sizeof(TO) == 2) {
                         u32x2_t w; w[0] = pack2<TO>(v[0], v[1]); w[1] = pack2<TO>(v[2], v[3]);
                         *(u32x2_t*)dst = w;
@@ -1390,6 +1396,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                         if (col + e < p.N) {
                             float y = v[e];
                             if (resp) y += load_out<TO>(resp + (long long)row * p.ldr + col + e);
+                            if (p.act == RF_ACT_ADD_RELU) y = fmaxf(y, 0.0f);
                             store_out<TO>(dst + e, y);
                             if (gn_on) {
                                 float ys = y;
@@ -1670,7 +1677,7 @@ __global__ __launch_bounds__(64 * TN) void splitk_reduce_frag_kernel(const GemmP
 // fraction of the 256 CUs left idle, plus the fp32 partial-sum traffic (write + re-read of sk * M * N floats at ~4 TB/s).
 static int pick_splitk(const rf_conv_gemm_desc* d, const GemmParams& p, long long tiles, int bk) {
     const int nk = (p.K + bk - 1) / bk;
-    if (!d->workspace || d->batch != 1 || d->act == RF_ACT_GEGLU || tiles >= 200 || nk < 16) return 1;
+    if (!d->workspace || d->batch != 1 || d->act == RF_ACT_GEGLU || d->act == RF_ACT_ADD_RELU || tiles >= 200 || nk < 16) return 1;          // (ADD_RELU: the reduce passes act before the residual)
     int maxsk = nk / 8;
     if (maxsk > 16) maxsk = 16;
     const double t_gemm = 2.0 * p.M * p.N * (double)p.K / 6e14;
@@ -1774,7 +1781,7 @@ static int launch_cfg(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hipS
     constexpr bool DIRECT_OK = (WM * WN == 8) || (TM * TN == 5) || (TM * TN >= 16) || std::is_same<T, fp8_t>::value;      // (fp8 x fp8: every tile --
                                                                                           // the GEGLU epilogue with fp8 output exists only in this form)
     const bool ep_common = p.glds && p.epi2_ok && p.splitk == 1 && (!p.rowvec || p.rows_per_sample % BM == 0) &&
-                           (d->act == RF_ACT_NONE || (d->act == RF_ACT_GEGLU && TN % 2 == 0));
+                           (d->act == RF_ACT_NONE || d->act == RF_ACT_ADD_RELU || (d->act == RF_ACT_GEGLU && TN % 2 == 0));
     const bool direct = DIRECT_OK && ep_common && (p.gn_rows == 0 || d->act == RF_ACT_NONE);
     RF_CHECK(!hx || (HX_OK && conv && p.glds && p.KH == 3 && p.KW == 3 && p.stride == 1 && !p.ups && p.pad_t == 1 && p.pad_l == 1 && p.Hin == p.Hout &&
                      p.Win == p.Wout && p.Wout >= 16 && BM % p.Wout == 0 && (BM / p.Wout) * (p.Wout + 2) <= AXR_ &&
@@ -2063,6 +2070,9 @@ static int conv_gemm_impl(const rf_conv_gemm_desc* d, void* stream, int* plan) {
     RF_CHECK(d->korder != 2 || ((d->dtype == RF_BF16 || h16) && d->out_dtype == d->dtype && d->w_dtype == 0 && d->C1 == 0 && d->batch == 1),
              "rf_conv_gemm: korder=2 (row-extended A tiles) is built for bf16 -> bf16 / fp16 -> fp16 convolutions of one source");
     RF_CHECK(d->act != RF_ACT_PRELU || d->act_vec, "rf_conv_gemm: PReLU needs act_vec (per-column slopes)");
+    RF_CHECK(d->act >= RF_ACT_NONE && d->act <= RF_ACT_ADD_RELU, "rf_conv_gemm: bad act %d", d->act);
+    RF_CHECK(d->act != RF_ACT_ADD_RELU || (!d->ln_stats_in && !d->ln_stats_out && !oq),
+             "rf_conv_gemm: ReLU after the residual (RF_ACT_ADD_RELU) does not combine with LayerNorm folding or fp8 output");
     const bool conv = !(d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad_t == 0 && d->pad_l == 0 && d->ups == 0 &&
                         d->C1 == 0 && d->Hin == d->Hout && d->Win == d->Wout);
     RF_CHECK(!conv || d->batch == 1, "rf_conv_gemm: batch > 1 only for plain GEMM");

@@ -10,7 +10,7 @@ import threading
 import torch
 
 from . import _lib
-from ._lib import (ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_PRELU, ACT_QUICK_GELU, ACT_RELU, ACT_SIGMOID, ACT_SILU, RF_BF16, RF_BF16X3, RF_F16, RF_F32,
+from ._lib import (ACT_ADD_RELU, ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_PRELU, ACT_QUICK_GELU, ACT_RELU, ACT_SIGMOID, ACT_SILU, RF_BF16, RF_BF16X3, RF_F16, RF_F32,
                    RF_FP8_E4M3, AttnInDesc, ConvGemmDesc, FfnDesc, StemDesc)
 
 # Attention scores in the exp2 domain: the UNet folds d^-0.5 * log2(e) into the to_q weights and calls rf_attention with scale = ln 2
@@ -1061,6 +1061,54 @@ def pose_distance(deg_res, deg_tgt, labels, dist, totals, name="pose_distance"):
     assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.shape == (M,)
     assert dist.dtype == totals.dtype == torch.float64 and dist.is_contiguous() and dist.shape == (M,) and totals.is_contiguous() and totals.shape == (2,)
     return Launch(lib.rf_pose_distance, (_p(deg_res), M, _p(deg_tgt), N, _p(labels), _p(dist), _p(totals)), (deg_res, deg_tgt, labels, dist, totals), name)
+
+
+def expr_prep_u8(images_u8, xtaps, ytaps, out, name="expr_prep_u8"):
+    """The expression metric's item preparation in one launch (rf_expr_prep_u8): images uint8 [B, H, W, 3] (packed images, any image stride,
+    any H, W >= 1) -> out fp32 NHWC [B, 512, 512, 8] = PIL's resize((512, 512), BICUBIC) bytes / 255 in channels 0..2, zeros in 3..7.
+    xtaps / ytaps = (bounds int32 [512, 2], taps int32 [512, ksize]) on the device: reface_amd.align.resample_taps(W | H, 512, "bicubic")."""
+    lib = _lib.load()
+    (xb, xk), (yb, yk) = xtaps, ytaps
+    _require_gpu(images_u8, xb, xk, yb, yk, out)
+    B, H, W_, C3 = images_u8.shape
+    assert images_u8.dtype == torch.uint8 and C3 == 3
+    assert images_u8.stride(3) == 1 and images_u8.stride(2) == 3 and images_u8.stride(1) == W_ * 3
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B, 512, 512, 8), tuple(out.shape)
+    for b, k in ((xb, xk), (yb, yk)):
+        assert b.dtype == k.dtype == torch.int32 and b.is_contiguous() and k.is_contiguous() and b.shape == (512, 2) and k.ndim == 2 and k.shape[0] == 512
+    return Launch(lib.rf_expr_prep_u8, (_p(images_u8), B, H, W_, images_u8.stride(0) if B > 1 else H * W_ * 3, _p(xb), _p(xk), xk.shape[1], _p(yb), _p(yk),
+                                        yk.shape[1], _p(out)), (images_u8, xb, xk, yb, yk, out), name)
+
+
+def expr_head(feat, w257, b257, coeffs, name="expr_head"):
+    """net_recon's head (rf_expr_head): layer4 features fp32 [B, P, 2048] (or [B, h, w, 2048], P = h * w), the stacked final_layers weights
+    [257, 2048] and bias [257] -> coefficients fp32 [B, 257].  One workgroup per image: the result does not depend on B."""
+    lib = _lib.load()
+    _require_gpu(feat, w257, b257, coeffs)
+    B = feat.shape[0]
+    P = feat.numel() // (B * 2048)
+    assert feat.dtype == w257.dtype == b257.dtype == coeffs.dtype == torch.float32
+    assert feat.shape[-1] == 2048 and feat.numel() == B * P * 2048 and feat.is_contiguous() and w257.shape == (257, 2048) and w257.is_contiguous()
+    assert b257.shape == (257,) and b257.is_contiguous() and coeffs.shape == (B, 257) and coeffs.is_contiguous()
+    return Launch(lib.rf_expr_head, (_p(feat), B, P, _p(w257), _p(b257), _p(coeffs)), (feat, w257, b257, coeffs), name)
+
+
+def expr_distance(coef_res, coef_tgt, labels, dist, totals, *, col0=80, ncols=64, name="expr_distance"):
+    """L2 distances over columns [col0, col0 + ncols) of result coefficients fp32 [M, ld] to target coefficients fp32 [N, ld] picked by labels
+    int32 [M] (rf_expr_distance): dist fp64 [M], totals fp64 [2] = (sum of dist, M), in fp64 and in a fixed summation order.  The labels must
+    lie in [0, N): IndexError otherwise (the labels are read back once, when the launch is prepared)."""
+    lib = _lib.load()
+    _require_gpu(coef_res, coef_tgt, labels, dist, totals)
+    M, ld = coef_res.shape
+    N = coef_tgt.shape[0]
+    assert coef_res.dtype == coef_tgt.dtype == torch.float32 and coef_tgt.shape == (N, ld) and coef_res.is_contiguous() and coef_tgt.is_contiguous()
+    assert 0 <= col0 and 0 < ncols and col0 + ncols <= ld
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.shape == (M,)
+    assert dist.dtype == totals.dtype == torch.float64 and dist.is_contiguous() and dist.shape == (M,) and totals.is_contiguous() and totals.shape == (2,)
+    if M == 0 or N == 0 or int(labels.min()) < 0 or int(labels.max()) >= N:
+        raise IndexError(f"labels must be {M} indices into the {N} targets")
+    return Launch(lib.rf_expr_distance, (_p(coef_res), M, _p(coef_tgt), N, ld, col0, ncols, _p(labels), _p(dist), _p(totals)),
+                  (coef_res, coef_tgt, labels, dist, totals), name)
 
 
 def label_mask(labels_u8, lut256, out, *, invert, name="label_mask"):

@@ -471,6 +471,33 @@ def hopenet_param_specs(num_bins=66):
     return s
 
 
+RECON_FINAL_DIMS = (80, 64, 80, 3, 27, 2, 1)          # id, exp, tex, angle, gamma, (tx, ty), tz: 257 coefficients
+
+
+def recon_param_specs():
+    """State-dict keys of Deep3DFaceRecon's ``ReconNetWrapper('resnet50', use_last_fc=False)`` (models/networks.py:69-104, 210-376), in module
+    order: ``backbone.*`` is a ResNet-50 without ``fc`` (the Bottlenecks of hopenet_units()), ``final_layers.0..6`` the seven 1x1
+    convolutions with bias on the pooled features."""
+    s = OrderedDict()
+    s["backbone.conv1.weight"] = (64, 3, 7, 7)
+    _bn(s, "backbone.bn1", 64)
+    for p, cin, planes, stride in hopenet_units():
+        p = f"backbone.{p}"
+        s[f"{p}.conv1.weight"] = (planes, cin, 1, 1)
+        _bn(s, f"{p}.bn1", planes)
+        s[f"{p}.conv2.weight"] = (planes, planes, 3, 3)
+        _bn(s, f"{p}.bn2", planes)
+        s[f"{p}.conv3.weight"] = (planes * 4, planes, 1, 1)
+        _bn(s, f"{p}.bn3", planes * 4)
+        if stride != 1 or cin != planes * 4:
+            s[f"{p}.downsample.0.weight"] = (planes * 4, cin, 1, 1)
+            _bn(s, f"{p}.downsample.1", planes * 4)
+    for i, n in enumerate(RECON_FINAL_DIMS):
+        s[f"final_layers.{i}.weight"] = (n, 2048, 1, 1)
+        s[f"final_layers.{i}.bias"] = (n,)
+    return s
+
+
 def cond_head_specs():
     """Top-level LatentDiffusion conditioning heads (ddpm.py:698-733)."""
     s = OrderedDict()

@@ -8,7 +8,7 @@ as small ``.npz`` fixtures under tests/golden/.  Only DATA is stored (tensors + 
 needed to regenerate the weights); no reference source is copied.
 
 Usage:  python tools/gen_golden.py [group ...]     (groups: schedule unet_ops unet_small unet_full
-                                                    ddim vae arcface clip e2e bisenet align idscore pose)
+                                                    ddim vae arcface clip e2e bisenet align idscore pose expr)
 """
 import os
 import sys
@@ -898,9 +898,134 @@ def gen_pose():
          e_ref=np.float64(e_ref), seed=PS.SEED)
 
 
+def gen_expr():
+    """The expression metric (eval_tool/Expression/expression_compare_face_recon.py over Deep3DFaceRecon's models/networks.py): the reference's
+    own ReconNetWrapper('resnet50', use_last_fc=False), ParametricFaceModel.split_coeff (bfm.py; it does not touch ``self``), ImagePathDataset,
+    compute_features, compute_features_wrapp and calculate_id_given_paths on the seeded PNG folders of tests/expr_inputs.py, with the seeded
+    weights of reface_amd.exprscore.seeded_recon_state in place of the checkpoint file.  All three files are loaded by path.  What was stubbed,
+    exactly: ``kornia.geometry.warp_affine`` (imported by networks.py, used by the recognition net only), ``util.load_mats.transferBFM09``
+    (imported by bfm.py, used by the face model's constructor only), ``cv2`` and the torchvision transforms (imported by the script; its
+    ImagePathDataset builds two Compose objects it never applies), tqdm / scipy when absent, ``options.test_options.TestOptions`` (the script
+    parses it at import; nothing of it is read here) and ``models.create_model``: the real FaceReconModel needs BFM_model_front.mat,
+    nvdiffrast and trimesh, so a stand-in takes its place whose ``forward`` is the real one's two lines (facerecon_model.py:136-147),
+    ``split_coeff(net_recon(x))``, and whose ``setup`` loads ``torch.load(...)['net_recon']`` strictly as base_model.load_networks does
+    (torch.load returns the seeded state).  Stored: the state-dict key layout of the reference module, the labels, all 257 coefficients of
+    every image in fp32 (the reference as it runs) and from the same module and inputs in float64, the distances and Expression_value of
+    both, e_ref = max |exp_f32 - exp_f64| over the 18 x 64 expression coefficients and e_ref_all, the same over all 257.  A degenerate
+    fixture is refused, against the distance gate of the tests (64 x e_ref): every expression coefficient must vary by >= 100 x e_ref (std)
+    over the images, Expression_value >= 100 gates, and labelling by the last number or pairing by position must each move Expression_value
+    by more than 10 gates."""
+    import importlib
+    import importlib.util
+    import tempfile
+    import types
+    sys.path.insert(1, os.path.join(os.path.dirname(HERE), "tests"))
+    import expr_inputs as I
+    from reface_amd import exprscore as ES
+
+    for name in ("tqdm", "scipy"):
+        try:
+            importlib.import_module(name)
+        except ImportError:
+            m = ref_shims._mod(name)
+            m.tqdm = lambda it, **k: it
+            m.linalg = None
+    _install_tv_transforms()
+    ref_shims._mod("cv2")
+    ref_shims._mod("kornia.geometry").warp_affine = None
+    ref_shims._mod("util")
+    ref_shims._mod("util.load_mats").transferBFM09 = None
+    D3 = "/root/reference/eval_tool/Deep3DFaceRecon_pytorch_edit"
+
+    def by_path(name, path):
+        spec = importlib.util.spec_from_file_location(name, path)
+        m = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(m)
+        return m
+
+    N = by_path("ref_d3_networks", D3 + "/models/networks.py")
+    BFM = by_path("ref_d3_bfm", D3 + "/models/bfm.py")
+    split_coeff = BFM.ParametricFaceModel.split_coeff
+    sd = ES.seeded_recon_state()
+
+    class StandIn(torch.nn.Module):
+        """FaceReconModel without the renderer and the face model: net_recon + split_coeff."""
+
+        def __init__(self, opt):
+            super().__init__()
+            self.net_recon = N.define_net_recon(net_recon="resnet50", use_last_fc=False, init_path=None)
+            self.facemodel = types.SimpleNamespace(to=lambda *a, **k: None)
+
+        def setup(self, opt):
+            self.net_recon.load_state_dict(torch.load("Other_dependencies/face_recon/epoch_latest.pth", map_location="cpu")["net_recon"])
+
+        def forward(self, x):
+            return split_coeff(None, self.net_recon(x))
+
+    ref_shims._mod("eval_tool.Deep3DFaceRecon_pytorch_edit")
+    ref_shims._mod("eval_tool.Deep3DFaceRecon_pytorch_edit.options")
+    to = ref_shims._mod("eval_tool.Deep3DFaceRecon_pytorch_edit.options.test_options")
+    to.TestOptions = lambda *a, **k: types.SimpleNamespace(parse=lambda: types.SimpleNamespace())
+    ref_shims._mod("eval_tool.Deep3DFaceRecon_pytorch_edit.models").create_model = StandIn
+    R = by_path("ref_expression_compare", "/root/reference/eval_tool/Expression/expression_compare_face_recon.py")
+
+    net = N.define_net_recon(net_recon="resnet50", use_last_fc=False, init_path=None).eval()
+    ref_sd = net.state_dict()
+    keys = np.array(list(ref_sd.keys()))
+    shapes = np.array([",".join(str(d) for d in v.shape) for v in ref_sd.values()])
+    net.load_state_dict(sd, strict=True)
+    net64 = N.define_net_recon(net_recon="resnet50", use_last_fc=False, init_path=None).eval()
+    net64.load_state_dict(sd, strict=True)
+    net64.double()
+
+    data = I.build()
+    labels = data["labels"]
+    dev = torch.device("cpu")
+    with tempfile.TemporaryDirectory() as tmp:
+        paths = I.write_folders(tmp, data)
+        load = torch.load
+        torch.load = lambda *a, **k: {"net_recon": sd}          # the checkpoint path of the stand-in's setup
+        try:
+            value, sims = R.calculate_id_given_paths(paths, 50, dev, 2048, 0)
+            model = StandIn(None)
+            model.setup(None)
+        finally:
+            torch.load = load
+        model.eval()
+        _, ref_labels = R.compute_features_wrapp(paths[1], model, 50, 2048, dev, 0)
+        assert list(ref_labels) == labels.tolist(), (ref_labels, labels)
+        lists = [sorted(os.path.join(p, n) for n in os.listdir(p)) for p in paths]
+        assert [os.path.basename(f) for f in lists[0]] == data["tgt_names"] and [os.path.basename(f) for f in lists[1]] == data["res_names"]
+        x = [[R.ImagePathDataset(files)[i] for i in range(len(files))] for files in lists]          # [1, 3, 512, 512] each
+    coef32 = [net(torch.cat(xs)).numpy() for xs in x]          # one batch per folder, as the script ran them (its batch of 50 becomes the folder)
+    coef64 = [torch.cat([net64(t.double()) for t in xs]).numpy() for xs in x]
+    assert coef32[0].shape == (10, 257) and coef32[0].dtype == np.float32 and coef64[0].dtype == np.float64
+
+    h32 = ES.score_host(coef32[0], coef32[1], labels)
+    h64 = ES.score_host(coef64[0], coef64[1], labels)
+    assert abs(h32["expression_value"] - float(value)) <= 1e-12 * abs(float(value)) and np.abs(np.asarray(sims) - h32["distances"]).max() <= 1e-12, (h32["expression_value"], value)
+    sl = slice(ES.EXP0, ES.EXP0 + ES.EXP_N)
+    e_ref = max(float(np.abs(a[:, sl] - b[:, sl]).max()) for a, b in zip(coef32, coef64))
+    e_ref_all = max(float(np.abs(a - b).max()) for a, b in zip(coef32, coef64))
+    gate = 64.0 * e_ref
+    std = np.concatenate(coef64)[:, sl].std(axis=0)
+    by_last = ES.score_host(coef64[0], coef64[1], I.last_number_labels())["expression_value"]
+    by_position = ES.score_host(coef64[0], coef64[1], list(range(len(labels))))["expression_value"]
+    print(f"  Expression_value fp32 {h32['expression_value']:.6f}  fp64 {h64['expression_value']:.6f}  e_ref {e_ref:.3e}  e_ref_all {e_ref_all:.3e}  gate {gate:.3e}")
+    print(f"  distances {np.round(h64['distances'], 4).tolist()}")
+    print(f"  per-coefficient std min {std.min():.3e} max {std.max():.3e}; max |coef| {np.abs(np.concatenate(coef64)).max():.3f}")
+    print(f"  Expression_value with last-number labels {by_last:.6f}, paired by position {by_position:.6f}")
+    if std.min() < 100 * e_ref or h64["expression_value"] < 100 * gate:
+        raise SystemExit(f"gen_expr: degenerate fixture (std min {std.min():.3e} vs 100 e_ref {100 * e_ref:.3e}; value {h64['expression_value']:.3e} vs 100 gates {100 * gate:.3e})")
+    assert abs(by_last - h64["expression_value"]) > 10 * gate and abs(by_position - h64["expression_value"]) > 10 * gate, "the fixture must expose a wrong labelling and a wrong pairing"
+    save("expr", keys=keys, shapes=shapes, labels=labels, coef_f32_tgt=coef32[0], coef_f32_res=coef32[1], coef_f64_tgt=coef64[0], coef_f64_res=coef64[1],
+         dist_f32=h32["distances"], dist_f64=h64["distances"], expression_value_f32=np.float64(h32["expression_value"]),
+         expression_value_f64=np.float64(h64["expression_value"]), e_ref=np.float64(e_ref), e_ref_all=np.float64(e_ref_all), seed=ES.SEED)
+
+
 GROUPS = dict(ddim_full=gen_ddim_full, unet_keys=gen_unet_keys, plms=gen_plms, schedule=gen_schedule, unet_ops=gen_unet_ops, unet_small=gen_unet_small, unet_full=gen_unet_full,
               ddim=gen_ddim, vae=gen_vae, arcface=gen_arcface, clip=gen_clip, e2e=gen_e2e,
-              bisenet=gen_bisenet, align=gen_align, idscore=gen_idscore, pose=gen_pose)
+              bisenet=gen_bisenet, align=gen_align, idscore=gen_idscore, pose=gen_pose, expr=gen_expr)
 
 if __name__ == "__main__":
     sel = sys.argv[1:] or [g for g in GROUPS if g != "ddim_full"]          # (ddim_full: 20 minutes; ask for it by name)
