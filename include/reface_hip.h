@@ -71,6 +71,14 @@ typedef struct rf_conv_gemm_desc {
     int32_t Hin, Win;     /* spatial size of the stored source (before `ups`) */
     int32_t Hout, Wout;   /* spatial size of the output; M = B*Hout*Wout */
     int32_t KH, KW, stride, pad_t, pad_l, ups;
+    /* ups: 0 none.  1: the window runs over the nearest-x2 upsampled source (address >> 1; Hout x Wout = 2 Hin x 2 Win for 3x3 / stride 1 / pad 1). */
+    /* 2: the same 3x3 convolution with the upsampling folded into the WEIGHTS: output pixel (2i + py, 2j + px) is a 2x2 window of the stored source */
+    /* at (i - 1 + py + ty, j - 1 + px + tx) on phase weights Wf[py][px][n][ty][tx][c] = sum of the 3x3 taps that land on that source pixel (rows */
+    /* {0}, {1, 2} for py = 0 and {0, 1}, {2} for py = 1, columns alike): K = 4 C0 instead of 9 C0.  Descriptor: KH = KW = 2, stride 1, pad_t = pad_l = 1 */
+    /* (phase (0, 0)'s; phase (py, px) pads (1 - py, 1 - px)), Hout = 2 Hin, Wout = 2 Win, M = B Hout Wout with GEMM rows ordered (sample, phase = */
+    /* 2 py + px, i, j) -- `out` is still addressed by pixel --, W = the four [N][ldw] matrices one behind the other.  bf16 / fp16 operands on the */
+    /* direct-to-LDS loop (C0 a multiple of 64), one source, batch 1, korder 0 / 1, no srcx / residual / rowvec / LayerNorm fold / GEGLU / fp8, no */
+    /* split-K, and Hin * Win a multiple of the tile rows (rf_conv_gemm_plan2 fails otherwise); fused GroupNorm statistics work as usual. */
     const void* W;        /* [N][K] row-major with row pitch ldw */
     int32_t ldw;          /* row pitch of W in elements (0 = K) */
     const float* bias;    /* [N] fp32 or NULL */

@@ -236,6 +236,20 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
     const T* src1 = (const T*)p.src1;
     const T* Wp = W8 ? (const T*)((const char*)p.W + zb * p.sW) : (const T*)p.W + zb * p.sW;
     if (!W8 && p.w_ps) Wp += (long long)(m0 / p.rows_per_sample) * p.w_ps;          // (a tile lies inside one sample: host)
+    // ups == 2 (nearest-2x upsampling folded into 2x2 phase weights): rows are ordered (sample, phase = 2 py + px, source pixel) and a tile lies
+    // inside one phase of one sample (host: Hin Win % BM == 0), so the phase, its padding (1 - py, 1 - px) and its weights W[phase] are block-uniform
+    const int hw_in = p.Hin * p.Win;
+    const int uph = (CONV && p.ups == 2) ? (m0 / hw_in) & 3 : 0;
+    if (!W8 && uph) Wp += (long long)uph * p.N * p.ldw;
+    const bool up2 = CONV && p.ups == 2;
+    const int pad_t = up2 ? 1 - (uph >> 1) : p.pad_t, pad_l = up2 ? 1 - (uph & 1) : p.pad_l;
+    // row of `out` that GEMM row `row` of this tile writes: the row itself, or (ups == 2) pixel (2 i + py, 2 j + px) of its sample
+    auto out_row = [&](int row) -> int {
+        if (!up2) return row;
+        const int s4 = m0 / (4 * hw_in), r = row - (s4 * 4 + uph) * hw_in;
+        const int i = r / p.Win, j = r - i * p.Win;
+        return (s4 * p.Hout + 2 * i + (uph >> 1)) * p.Wout + 2 * j + (uph & 1);
+    };
 
     // EPI 1: the per-column constants of this tile (bias + the tile's timestep / context vector) are fetched NOW, one column per
     // thread, and parked in LDS after the main loop: fetched in the epilogue they cost one exposed L2 / HBM round trip per
@@ -283,7 +297,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
             if (++kx == p.KW) { kx = 0; ++ky; }
         }
     }
-    const int Hv = p.ups ? p.Hin * 2 : p.Hin, Wv = p.ups ? p.Win * 2 : p.Win;
+    const int Hv = p.ups == 1 ? p.Hin * 2 : p.Hin, Wv = p.ups == 1 ? p.Win * 2 : p.Win;          // (ups == 2 addresses the stored grid)
 
     // advance this thread's K position to the next K tile
     auto advance_k = [&]() {
@@ -452,8 +466,10 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                 rowd[i] = (ir < BM / p.Wout && R * p.Wout < p.M) ? ((unsigned)b << 20 | (unsigned)oy << 10 | (unsigned)xc) : ~0u;
             } else if (CONV) {
                 const int hw = p.Hout * p.Wout;
-                const int b = m / hw, rem = m - b * hw;
-                const int oy = rem / p.Wout, ox = rem - oy * p.Wout;
+                const int b = m / hw;
+                int rem = m - b * hw, wd = p.Wout;
+                if (up2) { rem -= uph * hw_in; wd = p.Win; }          // (oy, ox): the pixel of the SOURCE grid inside this tile's phase
+                const int oy = rem / wd, ox = rem - oy * wd;
                 rowd[i] = m < p.M ? ((unsigned)b << 20 | (unsigned)oy << 10 | (unsigned)ox) : ~0u;
             } else {
                 offs[i] = m < p.M ? m * p.ld0 * (int)sizeof(T) + lane_k : OOB;
@@ -470,16 +486,17 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                 offs[i] = ok ? (((int)(d >> 20) * p.Hin + iy) * p.Win + ix) * ld * (int)sizeof(T) + lane_k : OOB;
             }
         };
-        // A-piece offsets of filter tap (ty, tx): padding / upsampling / stride live here, once per tap
+        // A-piece offsets of filter tap (ty, tx): padding / upsampling / stride live here, once per tap (ups == 2: a stride-1 2x2 window of the stored
+        // grid with this tile's phase padding -- no shift)
         // (ld: pixel pitch of the source -- src0, or the tail source read at the tap (pad_t, pad_l), which is the output pixel: stride 1, no ups)
         auto set_tap = [&](int ty, int tx, int ld) {
 #pragma unroll
             for (int i = 0; i < AV; ++i) {
                 const unsigned d = rowd[i];
-                int iy = (int)((d >> 10) & 1023u) * p.stride - p.pad_t + ty;
-                int ix = (int)(d & 1023u) * p.stride - p.pad_l + tx;
+                int iy = (int)((d >> 10) & 1023u) * p.stride - pad_t + ty;
+                int ix = (int)(d & 1023u) * p.stride - pad_l + tx;
                 const bool ok = d != ~0u && (unsigned)iy < (unsigned)Hv && (unsigned)ix < (unsigned)Wv;
-                if (p.ups) { iy >>= 1; ix >>= 1; }
+                if (p.ups == 1) { iy >>= 1; ix >>= 1; }
                 offs[i] = ok ? (((int)(d >> 20) * p.Hin + iy) * p.Win + ix) * ld * (int)sizeof(T) + lane_k : OOB;
             }
             if constexpr (A8) {
@@ -1080,6 +1097,9 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
             constexpr bool ln_p = LNF == 1;                      // this launch also emits the LayerNorm row statistics of its output
             const bool keep_on = gn_on || ln_p;                  // the values as stored replace the (dead) accumulators
             float* const gcs = (float*)(smem + 2048);            // [2][WM][BN] column sums / sums of squares per wave row
+            int orow[TM];                                        // rows of `out` this lane writes (ups == 2: the phase's pixels, out_row)
+#pragma unroll
+            for (int i = 0; i < TM; ++i) orow[i] = out_row(m0 + (wm * TM + i) * 32 + lrow);
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 const int col = n0 + (wn * TN + j) * 32 + lhalf * 16;
@@ -1100,7 +1120,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                     const u32x4_t* const myr = rq[blk % PFD];
                     const bool live = row < p.M && cok;
                     if (live) {
-                        TO* dst = outp + (long long)row * p.ldo + col;
+                        TO* dst = outp + (long long)orow[i] * p.ldo + col;
 #pragma unroll
                         for (int h = 0; h < OV; ++h) {
                             constexpr int E = 16 / OV;
@@ -1329,6 +1349,16 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
             }
         }
         typedef typename std::conditional<sizeof(TO) == 2, u32x2_t, f32x4_t>::type resv_t;
+        // ups == 2: this thread's rows are EROWS apart, so their pixels follow incrementally -- out_row (two divisions) once per chunk; a step of
+        // (ostep_i source rows, ostep_j columns) with a carry over the source row's end: two rows of `out` further, 2 Win columns back = + Wout
+        int orow_cur = 0, oj = 0, ostep = 0, ostep_j = 0;
+        if (up2) {
+            const int r = (mch + er) % hw_in, ostep_i = EROWS / p.Win;
+            orow_cur = out_row(mch + er);
+            oj = r % p.Win;
+            ostep_j = EROWS - ostep_i * p.Win;
+            ostep = 2 * ostep_i * p.Wout + 2 * ostep_j;
+        }
 #pragma unroll 1
         for (int k0 = 0; k0 < PASSES; k0 += U) {
             resv_t rq[U];
@@ -1341,6 +1371,11 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
+                const int orow_u = orow_cur;
+                if (up2) {
+                    orow_cur += ostep; oj += ostep_j;
+                    if (oj >= p.Win) { oj -= p.Win; orow_cur += p.Wout; }
+                }
                 if (!ok[u]) continue;
                 const int rl = er + (k0 + u) * EROWS, row = mch + rl;
                 const f32x4_t a4 = *(const f32x4_t*)(stage + rl * BN + cl);
@@ -1363,7 +1398,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gemm_kernel(const GemmParams
                         v[e] = y;
                     }
                 }
-                TO* dst = outp + (long long)row * p.ldo + col;
+                TO* dst = outp + (long long)(up2 ? orow_u : row) * p.ldo + col;
                 if (full) {
                     if (resp) {
                         if constexpr (sizeof(TO) == 2) {
@@ -1797,6 +1832,9 @@ static int launch_cfg(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hipS
              "rf_conv_gemm: ln_stats_out needs the direct epilogue (no split-K, act NONE) and ln_out_parts = N / %d (got %d; direct %d)", 32 * TN, p.ln_out_parts, (int)direct);
     RF_CHECK(!p.ln_in || (direct && p.ln_u && p.ln_in_parts >= 1 && p.ln_in_cols >= 1 && p.ln_eps > 0.f && BN <= 320),
              "rf_conv_gemm: ln_stats_in needs the direct epilogue (no split-K), ln_u, ln_in_parts / ln_in_cols >= 1 and ln_eps > 0 (direct %d)", (int)direct);
+    RF_CHECK(p.ups != 2 || (p.splitk == 1 && (p.Hin * p.Win) % BM == 0),
+             "rf_conv_gemm: ups 2 needs Hin * Win = %d to be a multiple of the %d-row tile (a tile inside one phase of one sample) and no split-K (this launch: %d)",
+             p.Hin * p.Win, BM, p.splitk);
     if (p.plan) {
         p.plan[0] = st_rows; p.plan[1] = st_cols; p.plan[2] = p.splitk; p.plan[3] = BM; p.plan[4] = BN; p.plan[5] = 32 * TN;
         p.plan[6] = direct ? 1 : 0; p.plan[7] = frag ? 1 : 0;
@@ -1937,7 +1975,7 @@ static int launch_typed(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hi
                 //  LayerNorm consumer needs)
                 const long long tail_nt_ = full_ >= 1 && mt256 > 0 ? nt - full_ * 256 / mt256 : 0;
                 if (!n320 && full_ >= 1 && rem_ * 5 >= 256 && rem_ * 5 <= 3 * 256 && (full_ * 256) % mt256 == 0 && mt128 * tail_nt_ >= 192 && p.gn_rows == 0 && !p.ln_out && !p.oscale &&
-                    !p.w_ps && !p.x3 && d->batch == 1 && (d->act == RF_ACT_NONE || d->act == RF_ACT_GEGLU)) {
+                    !p.w_ps && !p.x3 && p.ups != 2 && d->batch == 1 && (d->act == RF_ACT_NONE || d->act == RF_ACT_GEGLU)) {
                     const int n1 = (int)(full_ * 256 / mt256) * 256;                       // columns of the whole rounds
                     auto part = [&](int n_off, int n_len) {
                         GemmParams q = p;
@@ -2145,6 +2183,20 @@ static int conv_gemm_impl(const rf_conv_gemm_desc* d, void* stream, int* plan) {
             RF_CHECK(p.glds && (conv || d->C0 == d->K), "rf_conv_gemm: split-bf16 operands need the direct-to-LDS main loop (K and channel count multiples of 64) and C0 == K for plain GEMMs");
             p.K = 3 * d->K;          // virtual K: three passes per real K tile
         }
+    }
+    // ups == 2: nearest-2x upsampling folded into four 2x2 phase filters (W = [4][N][ldw], rows ordered (sample, phase, source pixel)); lives on the
+    // direct-to-LDS loop of the 16-bit kernels alone (the tile condition -- Hin Win a multiple of the tile rows, no split-K -- is launch_cfg's)
+    RF_CHECK(d->ups >= 0 && d->ups <= 2, "rf_conv_gemm: bad ups %d (0 none, 1 nearest x2 in the addressing, 2 nearest x2 folded into 2x2 phase weights)", d->ups);
+    if (d->ups == 2) {
+        RF_CHECK((d->dtype == RF_BF16 || h16) && d->w_dtype == 0, "rf_conv_gemm: ups 2 needs bf16 / fp16 operands and weights (dtype %d, w_dtype %d)", d->dtype, d->w_dtype);
+        RF_CHECK(d->KH == 2 && d->KW == 2 && d->stride == 1 && d->pad_t == 1 && d->pad_l == 1,
+                 "rf_conv_gemm: ups 2 needs KH = KW = 2, stride 1 and pad_t = pad_l = 1, the padding of phase (0, 0) (got %dx%d, stride %d, pad %d %d)", d->KH, d->KW, d->stride, d->pad_t, d->pad_l);
+        RF_CHECK(d->Hout == 2 * d->Hin && d->Wout == 2 * d->Win, "rf_conv_gemm: ups 2 needs Hout x Wout = 2 Hin x 2 Win (%dx%d -> %dx%d)", d->Hin, d->Win, d->Hout, d->Wout);
+        RF_CHECK(d->C1 == 0 && d->batch == 1, "rf_conv_gemm: ups 2 needs one source and batch 1 (C1 %d, batch %d)", d->C1, d->batch);
+        RF_CHECK(!xt && !d->residual && !d->rowvec && !d->ln_stats_in && !d->ln_stats_out && d->w_sample_stride == 0 && d->act != RF_ACT_GEGLU,
+                 "rf_conv_gemm: ups 2 takes no tail source (srcx), residual, rowvec, LayerNorm fold, per-sample weights or GEGLU");
+        RF_CHECK(d->korder == 0 || d->korder == 1, "rf_conv_gemm: ups 2 needs korder 0 or 1 (got %d)", d->korder);
+        RF_CHECK(p.glds, "rf_conv_gemm: ups 2 needs the direct-to-LDS main loop (C0 = %d a multiple of 64, 31-bit operand extents)", d->C0);
     }
     hipStream_t st = (hipStream_t)stream;
     p.wscale = d->wscale;

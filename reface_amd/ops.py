@@ -78,6 +78,31 @@ def pack_conv_weight(w, dtype, cin_pad=None, korder=0):
     return wp.reshape(co, kh * kw * cp).to(dtype).contiguous()
 
 
+def fold_ups_weight(w):
+    """3x3 weights of a convolution behind a nearest-2x upsampling, fp32 [N, C, 3, 3] -> the four 2x2 phase filters fp32 [4, N, 2, 2, C] (phase =
+    2 py + px, then tap-major, channels last: per phase the order pack_conv_weight produces).  A 3x3 window over the upsampled image only ever
+    touches a 2x2 window of the stored one: output pixel (2i + py, 2j + px) reads source pixels (i - 1 + py + ty, j - 1 + px + tx), ty, tx in
+    {0, 1}, and filter taps that land on the same source pixel add up -- rows R[0] = ({0}, {1, 2}), R[1] = ({0, 1}, {2}), columns alike.  The
+    zero padding of the upsampled image is the zero padding of the source.  Exact; pure torch (rf_conv_gemm's ups = 2 multiplies the result)."""
+    n, c, kh, kw = w.shape
+    assert kh == 3 and kw == 3, (kh, kw)
+    R = (((0,), (1, 2)), ((0, 1), (2,)))
+    wf = w if w.dtype == torch.float64 else w.float()          # (float64 passes through: the identity's own test)
+    out = torch.zeros((4, n, 2, 2, c), dtype=wf.dtype, device=w.device)
+    for py in range(2):
+        for px in range(2):
+            for ty in range(2):
+                for tx in range(2):
+                    out[2 * py + px, :, ty, tx, :] = sum(wf[:, :, ky, kx] for ky in R[py][ty] for kx in R[px][tx])
+    return out
+
+
+def pack_ups_weight(w, dtype):
+    """[N, C, 3, 3] fp32 -> the W operand of conv2d(..., ups=2): [4, N, 4 C] in `dtype`, folded in fp32 (fold_ups_weight) and rounded once."""
+    f = fold_ups_weight(w)
+    return f.reshape(4, f.shape[1], 4 * f.shape[4]).to(dtype).contiguous()
+
+
 def pack_x3(w2d):
     """fp32 GEMM weight [N, K] (K a multiple of 64, already in rf_conv_gemm's K order) -> the split-bf16 operand of the RF_BF16X3 mode:
     [N, 3K] bf16, per 64-element K tile [64 hi | 64 lo | 64 hi] with hi = bf16(w), lo = bf16(w - hi)."""
@@ -538,7 +563,17 @@ def conv2d(x, W, out, bias=None, *, ksize=3, stride=1, pad=(1, 1), ups=0, x2=Non
     on channels); W: packed [Cout, k*k*(C0+C1)]; out: [B, Hout, Wout, Cout].  x3: x is the split-bf16 form [B, Hin, Win, 2*C0] of an
     fp32 tensor and W comes from pack_x3 ([Cout, 3*k*k*C0]).
     tail: a second tensor [B, Hout, Wout, Cx] whose 1x1 convolution is summed into the same contraction (rf_conv_gemm_desc.srcx: the ResBlock's
-    skip_connection inside out_layers.3) -- W is then pack_conv_tail(W, w_1x1) = [Cout, k*k*C0 + Cx] and `bias` the sum of the two biases."""
+    skip_connection inside out_layers.3) -- W is then pack_conv_tail(W, w_1x1) = [Cout, k*k*C0 + Cx] and `bias` the sum of the two biases.
+    ups=2: the 3x3 convolution of the nearest-2x upsampled x as four 2x2 phase convolutions of x itself (K = 4 C0 instead of 9 C0): W comes from
+    pack_ups_weight ([4, Cout, 4*C0]), out is [B, 2 Hin, 2 Win, Cout]; ksize / stride / pad are the 3x3 convolution's (3, 1, (1, 1))."""
+    if ups == 2:
+        assert W.dim() == 3 and W.shape[0] == 4 and W.is_contiguous() and ksize == 3 and stride == 1 and tuple(pad) == (1, 1), (tuple(W.shape), ksize, stride, pad)
+        assert x2 is None and residual is None and rowvec is None and tail is None and not x3 and not isinstance(x, Fp8Act)
+        B, Hin, Win, C0 = x.shape
+        assert x.stride(3) == 1 and tuple(out.shape[:3]) == (B, 2 * Hin, 2 * Win) and out.stride(3) == 1 and W.shape[2] == 4 * C0
+        return conv_gemm(x, W, out, M=4 * B * Hin * Win, N=out.shape[3], K=4 * C0, C0=C0, ld0=x.stride(2), Hin=Hin, Win=Win, Hout=2 * Hin, Wout=2 * Win,
+                         KH=2, KW=2, stride=1, pad_t=1, pad_l=1, ups=2, bias=bias, rows_per_sample=4 * Hin * Win, act=act, act_vec=act_vec,
+                         ldo=out.stride(2), korder=korder, name=name)
     if isinstance(x, Fp8Act):             # C0 = the padded channel count (W from quantize_fp8_padded(w, k*k, C))
         B, Hin, Win, C0 = x.q.shape
         ld0 = x.q.stride(2)

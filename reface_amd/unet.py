@@ -134,6 +134,10 @@ class UNetEngine:
         # the statistics of both its GroupNorm consumers (csrc/smallconv.hip): REFACE_STEM_FUSE=0 keeps the implicit GEMM + the statistics pass
         self.stem_fuse = os.environ.get("REFACE_STEM_FUSE", "1") == "1"
         self.n_stem_fused = 0
+        # the Upsample convolutions as four 2x2 phase convolutions on folded weights, K = 4 C instead of 9 C (rf_conv_gemm ups = 2; 16-bit modes, where
+        # a tile fits inside one phase of one sample): REFACE_UPS_FOLD=0 keeps the 3x3 convolution over the upsampled addressing
+        self.ups_fold = os.environ.get("REFACE_UPS_FOLD", "1") != "0"
+        self._ups_folded, self.n_ups_folded = set(), 0
         # 3x3 convolutions whose 256-row tiles overhang whole rounds of the chip by a little are split by samples (_add_conv3): REFACE_SAMPLE_SPLIT=0 off
         self.sample_split = os.environ.get("REFACE_SAMPLE_SPLIT", "1") == "1"
         self.n_sample_split = 0
@@ -321,6 +325,26 @@ class UNetEngine:
         if self.x3 and x.dtype == torch.bfloat16:          # split-bf16 input (from _gn(split=True) / split_in): cin is half the stored width
             self.n_x3 += 1
             return ops.conv2d(x, ops.pack_x3(ops.pack_conv_weight(self.sd[wkey], F32)), out, self.f32(bkey), x3=True, name=name, **kw)
+        if (kw.get("ups", 0) == 1 and self.ups_fold and self.dt in H16 and not self.w8 and tail is None and cin % 64 == 0 and kw.get("rowvec") is None
+                and kw.get("residual") is None and (x.shape[1] * x.shape[2]) % 128 == 0):
+            # Upsample: a 3x3 window over the nearest-2x upsampled image only touches a 2x2 window of the stored one -- four 2x2 phase convolutions on
+            # weights folded once from the fp32 masters (ops.fold_ups_weight), K = 4 C instead of 9 C, as ONE launch (rf_conv_gemm ups = 2).  A tile
+            # must lie inside one phase of one sample: a source below or across the library's smallest tile (128 rows) is not asked at all (8x8, 24x24:
+            # nothing is folded or cached for them); whether THIS launch's tile fits, and without split-K, is the library's answer: ask for the plan.
+            # Only that refusal means "keep ups = 1" (and frees the folded copy again); any other error of the descriptor is a bug and propagates.
+            made = (wkey, "ups2") not in self._wpack
+            cand = ops.conv2d(x, self._packed(wkey, "ups2", lambda: ops.pack_ups_weight(self.sd[wkey], self.dt)), out, bias, name=name, **dict(kw, ups=2))
+            try:
+                ops.gemm_plan2(cand)
+                self._ups_folded.add(wkey)
+                self.n_ups_folded = len(self._ups_folded)
+                return cand
+            except ops._lib.RefaceHipError as e:
+                if "ups 2 needs Hin * Win" not in str(e):
+                    raise
+                del cand
+                if made:
+                    del self._wpack[(wkey, "ups2")]
         ko = ops.conv_korder(cin, self.dt) if self.korder_on else 0
         if (self.hx_on and self.dt in H16 and not self.w8 and not ko and cin % 64 == 0 and kw.get("stride", 1) == 1 and not kw.get("ups", 0)
                 and x.shape[1:3] == out.shape[1:3]):
