@@ -1,0 +1,73 @@
+#!/usr/bin/env python3
+"""FID of a swap run on the MI355X-native engines: the Frechet distance between the Gaussians fitted to the ``clip`` ViT-B/32 image features
+of two image folders -- the reference's eval_tool/fid/fid_score.py (whose "inception" returns ``clip_model.encode_image``), same positionals,
+options and printed line:
+
+    python eval_tool/fid/fid_score.py --device cuda <dataset images | stats.npz> <results>
+
+Each folder is listed as the reference lists it (``glob('*.ext')`` per image extension, sorted).  Everything between the decode and the
+mean / covariance runs on the GPU (reface_amd/fidscore.py: rf_fid_prep_u8, the vision tower, rf_fid_stats); the Frechet step is the
+reference's ``scipy.linalg.sqrtm`` on the host.  ``--dims`` is accepted and unused, as in the reference.  A path ending in ``.npz`` is read
+for its ``mu`` and ``sigma``.
+
+Additions (not in the reference): ``--clip_ckpt`` (the file ``clip.load`` caches; ``none`` = the seeded tower of the tests), ``--precision``,
+``--json FILE``, ``--save-stats FILE.npz`` (``mu`` and ``sigma`` of the first path: a large dataset folder is featurised once).
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def build_parser():
+    from reface_amd.fidscore import DEFAULT_CLIP_CKPT
+    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("--batch-size", type=int, default=50, help="Batch size to use")
+    p.add_argument("--num-workers", type=int, help="decode workers of the loader (default: the CPUs this process may run on, 8 at the most)")
+    p.add_argument("--device", type=str, default=None, help="cuda or cuda:<i>; the HIP kernels have no CPU path")
+    p.add_argument("--dims", type=int, default=2048, choices=[64, 192, 768, 2048], help="accepted and unused, as in the reference: the features are CLIP's 512")
+    p.add_argument("path", type=str, nargs=2, default=["dataset/FaceData/CelebAMask-HQ/CelebA-HQ-img", "results/test_bench/results"],
+                   help="Paths to the images or to .npz statistic files")
+    # ---- additions
+    p.add_argument("--clip_ckpt", type=str, default=DEFAULT_CLIP_CKPT,
+                   help="(addition) the ViT-B/32 file clip.load caches (TorchScript archive or state dict); 'none' = the seeded tower the tests use")
+    p.add_argument("--precision", type=str, default="full", choices=["full", "bf16"], help="(addition) tower arithmetic: fp32, or bf16 operands")
+    p.add_argument("--json", type=str, default=None,
+                   help="(addition) write the value, its four terms, image counts, images/s (decode to value; engine construction excluded) and the "
+                        "number of images prepared on the host to this file")
+    p.add_argument("--save-stats", type=str, default=None, help="(addition) write mu and sigma of the first path to this .npz file")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    import numpy as np
+    import torch
+    from reface_amd.fidscore import FidScorer, load_fid_clip_state
+    device = torch.device(args.device if args.device is not None else "cuda")
+    if device.type != "cuda":
+        raise SystemExit(f"fid_score: --device {args.device}: the HIP kernels run on the GPU only (there is no CPU fallback)")
+    num_workers = min(len(os.sched_getaffinity(0)), 8) if args.num_workers is None else args.num_workers
+    for p in args.path:
+        if not os.path.exists(p):
+            raise RuntimeError("Invalid path: %s" % p)
+    state, _ = load_fid_clip_state(args.clip_ckpt)
+    scorer = FidScorer(state, precision=args.precision, batch=args.batch_size, device=device)
+    r = scorer.score_folders(args.path, num_workers=num_workers)
+    fid_value = r["fid"]
+    print("FID: ", fid_value)
+    if args.save_stats:
+        np.savez(args.save_stats, mu=r["mu1"], sigma=r["sigma1"])
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump({k: r[k] for k in ("fid", "mean_term", "trace1", "trace2", "trace_covmean", "images1", "images2", "images", "host_prepared",
+                                         "images_per_s", "seconds")} | {"precision": args.precision}, f)
+    return r
+
+
+if __name__ == "__main__":
+    main()

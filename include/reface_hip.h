@@ -541,6 +541,23 @@ int rf_expr_prep_u8(const void* images_u8, int B, int H, int W, int64_t image_st
 int rf_expr_head(const float* feat, int B, int P, const float* w257, const float* b257, float* coeffs, void* stream);
 int rf_expr_distance(const float* coef_res, int M, const float* coef_tgt, int N, int ld, int col0, int ncols, const int* labels, double* dist,
                      double* totals, void* stream);
+
+/*
+ * The FID of the evaluation (eval_tool/fid/fid_score.py of the reference; its features are the `clip` ViT-B/32 image embeddings), the two
+ * passes around the vision tower (which runs on rf_conv_gemm, rf_attention and rf_layernorm):
+ *   rf_fid_prep_u8 : clip.load's preprocess.  images u8 [B, H, W, 3] (image b at images + b * image_stride bytes; any H, W >= 1) and the tap
+ *                    tables of PIL's BICUBIC resize of each axis to Resize(224)'s size, SLICED to the 224 outputs of CenterCrop(224)
+ *                    (xbounds / ybounds i32 [224, 2] = first input index and tap count, xk / yk i32 [224, ksize], 22-bit fixed point) ->
+ *                    out NHWC [B, 224, 224, CP] (16-byte aligned), out_dtype RF_F32 (CP = 4) or RF_BF16 (CP = 8):
+ *                    (float32(byte) / 255 - mean) / std in channels 0..2, each step rounded to fp32, zeros in the pad channels.  PIL's two
+ *                    integer passes with the u8 rounding between them; the horizontally resampled rows live in LDS only.
+ *   rf_fid_stats   : feat fp32 [N, D] (N >= 2, D a multiple of 16) -> mu fp64 [D] = the mean of the widened rows, sigma fp64 [D, D] =
+ *                    sum_i (x_i - mu)(x_i - mu)^T / (N - 1) on the fp64 MFMA, upper-triangle tiles mirrored from the same registers (sigma
+ *                    equals its transpose bit for bit).  Fixed summation order, no atomics: the same bits on every run.
+ */
+int rf_fid_prep_u8(const void* images_u8, int B, int H, int W, int64_t image_stride, const int* xbounds, const int* xk, int xksize,
+                   const int* ybounds, const int* yk, int yksize, int out_dtype, void* out, void* stream);
+int rf_fid_stats(const float* feat, int N, int D, double* mu, double* sigma, void* stream);
 /* elementwise y = silu(x) on fp32 (emb path, openaimodel.py:219) */
 int rf_silu_f32(const float* x, float* y, int64_t n, void* stream);
 

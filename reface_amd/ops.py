@@ -1146,6 +1146,36 @@ def expr_distance(coef_res, coef_tgt, labels, dist, totals, *, col0=80, ncols=64
                   (coef_res, coef_tgt, labels, dist, totals), name)
 
 
+def fid_prep_u8(images_u8, xtaps, ytaps, out, name="fid_prep_u8"):
+    """The FID's item preparation in one launch (rf_fid_prep_u8): images uint8 [B, H, W, 3] (packed images, any image stride, any H, W >= 1)
+    -> out NHWC [B, 224, 224, CP], fp32 (CP = 4) or bf16 (CP = 8) = clip's preprocess (Resize(224, BICUBIC), CenterCrop(224), ToTensor,
+    Normalize) in channels 0..2, zeros in the pad channels.  xtaps / ytaps = (bounds int32 [224, 2], taps int32 [224, ksize]) on the device:
+    reface_amd.align.resample_taps(W | H, resized size, "bicubic") sliced to the crop window (reface_amd.fidscore.crop_taps)."""
+    lib = _lib.load()
+    (xb, xk), (yb, yk) = xtaps, ytaps
+    _require_gpu(images_u8, xb, xk, yb, yk, out)
+    B, H, W_, C3 = images_u8.shape
+    assert images_u8.dtype == torch.uint8 and C3 == 3
+    assert images_u8.stride(3) == 1 and images_u8.stride(2) == 3 and images_u8.stride(1) == W_ * 3
+    assert out.dtype in (torch.float32, torch.bfloat16) and out.is_contiguous(), out.dtype
+    assert out.shape == (B, 224, 224, 4 if out.dtype == torch.float32 else 8), tuple(out.shape)
+    for b, k in ((xb, xk), (yb, yk)):
+        assert b.dtype == k.dtype == torch.int32 and b.is_contiguous() and k.is_contiguous() and b.shape == (224, 2) and k.ndim == 2 and k.shape[0] == 224
+    return Launch(lib.rf_fid_prep_u8, (_p(images_u8), B, H, W_, images_u8.stride(0) if B > 1 else H * W_ * 3, _p(xb), _p(xk), xk.shape[1], _p(yb), _p(yk),
+                                       yk.shape[1], code(out.dtype), _p(out)), (images_u8, xb, xk, yb, yk, out), name)
+
+
+def fid_stats(feat, mu, sigma, name="fid_stats"):
+    """Mean and covariance of feature rows (rf_fid_stats): feat fp32 [N, D] (N >= 2, D a multiple of 16) -> mu fp64 [D], sigma fp64 [D, D] =
+    np.mean(feat64, 0) and np.cov(feat64, rowvar=False) in a fixed summation order on the fp64 MFMA; sigma equals its transpose bit for bit."""
+    lib = _lib.load()
+    _require_gpu(feat, mu, sigma)
+    N, D = feat.shape
+    assert feat.dtype == torch.float32 and feat.is_contiguous()
+    assert mu.dtype == sigma.dtype == torch.float64 and mu.is_contiguous() and sigma.is_contiguous() and mu.shape == (D,) and sigma.shape == (D, D)
+    return Launch(lib.rf_fid_stats, (_p(feat), N, D, _p(mu), _p(sigma)), (feat, mu, sigma), name)
+
+
 def label_mask(labels_u8, lut256, out, *, invert, name="label_mask"):
     lib = _lib.load()
     _require_gpu(labels_u8, lut256, out)

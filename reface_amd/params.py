@@ -346,6 +346,16 @@ def clip_param_specs(cfg: CLIPVisionConfig):
     return s
 
 
+def fid_clip_param_specs(cfg: CLIPVisionConfig):
+    """The vision tower of the FID metric (reface_amd/fidscore.py) in HF ``CLIPVisionModelWithProjection`` naming: ``vision_model.*`` and
+    ``visual_projection.weight``, nothing behind the projection."""
+    s = OrderedDict()
+    for k, shp in clip_param_specs(cfg).items():
+        if k.startswith("model."):
+            s[k[len("model."):]] = shp
+    return s
+
+
 # --------------------------------------------------------------------------------------------
 # ArcFace IR-SE50
 # --------------------------------------------------------------------------------------------

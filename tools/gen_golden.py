@@ -8,7 +8,7 @@ as small ``.npz`` fixtures under tests/golden/.  Only DATA is stored (tensors + 
 needed to regenerate the weights); no reference source is copied.
 
 Usage:  python tools/gen_golden.py [group ...]     (groups: schedule unet_ops unet_small unet_full
-                                                    ddim vae arcface clip e2e bisenet align idscore pose expr)
+                                                    ddim vae arcface clip e2e bisenet align idscore pose expr fid)
 """
 import os
 import sys
@@ -1023,9 +1023,182 @@ def gen_expr():
          expression_value_f64=np.float64(h64["expression_value"]), e_ref=np.float64(e_ref), e_ref_all=np.float64(e_ref_all), seed=ES.SEED)
 
 
+def _hf_fid_tower(cfg: P.CLIPVisionConfig, sd):
+    """HF ``CLIPVisionModelWithProjection`` of ``cfg`` carrying the HF-named vision state ``sd`` (strict)."""
+    from transformers import CLIPVisionConfig, CLIPVisionModelWithProjection
+    c = CLIPVisionConfig(hidden_size=cfg.hidden, intermediate_size=cfg.intermediate, num_hidden_layers=cfg.layers, num_attention_heads=cfg.heads,
+                         patch_size=cfg.patch, image_size=cfg.image, projection_dim=cfg.proj, hidden_act="quick_gelu")
+    m = CLIPVisionModelWithProjection(c).eval()
+    have = m.state_dict()
+    remap = {k: (k if k in have else k.replace("vision_model.", "vision_model.vision_model.", 1)) for k in sd}
+    missing, unexpected = m.load_state_dict({remap[k]: v for k, v in sd.items()}, strict=False)
+    assert not unexpected and not [k for k in missing if "position_ids" not in k], (missing[:5], unexpected[:5])
+    return m
+
+
+def gen_fid():
+    """The FID (eval_tool/fid/fid_score.py over eval_tool/fid/inception.py): the reference's own InceptionV3.forward (which returns
+    ``clip_model.encode_image``), ImagePathDataset, get_activations, calculate_activation_statistics and calculate_frechet_distance on the
+    seeded PNG folders of tests/fid_inputs.py.  Both files are loaded by path.  What was stubbed, exactly: ``clip.load`` returns a stand-in
+    whose ``encode_image`` is the ``image_embeds`` of an HF ``CLIPVisionModelWithProjection`` (the fixture tower of reface_amd.fidscore with
+    its seeded weights) and the restated ``preprocess`` (torchvision's Resize(224, BICUBIC) / CenterCrop(224) / convert("RGB") / ToTensor /
+    Normalize: the sizes and the crop offset written out, PIL and torch doing the arithmetic); ``torchvision.models``' inception_v3,
+    InceptionA / C / E and load_state_dict_from_url (the reference still BUILDS an InceptionV3 it never runs: the stand-in has Identity
+    layers and loads nothing); and get_activations' hard-coded feature width, ``np.empty((n, 512))``, which becomes the fixture tower's
+    projection width through a numpy proxy on the loaded module.  Stored: three prepared tensors, both feature sets in fp32 and from the same
+    module in float64 and in bfloat16, e_ref_feat = max |f32 - f64| and e_ref_feat_bf16, mu / sigma / FID of the reference's float64 path,
+    fid_tol per precision (the largest |dFID| over 8 seeded uniform perturbations of the float64 features by +- 4 e_ref, doubled), and the
+    features of a ViT-B/32-sized seeded tower on 4 images with their own e_ref.  A degenerate fixture is refused: both covariances must have
+    full rank and the reference's sqrtm must come out finite and real without the eps retry."""
+    import contextlib
+    import importlib.util
+    import io
+    import tempfile
+    from PIL import Image
+    sys.path.insert(1, os.path.join(os.path.dirname(HERE), "tests"))
+    import fid_inputs as I
+    from reface_amd import fidscore as FS
+
+    sd, cfg = FS.load_fid_clip_state("none")
+    hf = _hf_fid_tower(cfg, sd)
+
+    def preprocess(im):
+        w, h = im.size
+        nh, nw = FS.resized_size(h, w)
+        if (nh, nw) != (h, w):
+            im = im.resize((nw, nh), Image.BICUBIC)
+        top, left = FS.crop_offset(nh), FS.crop_offset(nw)
+        im = im.crop((left, top, left + 224, top + 224)).convert("RGB")
+        t = torch.from_numpy(np.asarray(im, dtype=np.uint8).transpose(2, 0, 1).copy()).to(torch.float32).div(255)
+        return sys.modules["torchvision.transforms.functional"].normalize(t, (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711))
+
+    class ClipStandIn(torch.nn.Module):
+        def __init__(self, tower):
+            super().__init__()
+            self.tower = tower
+
+        def encode_image(self, x):
+            return self.tower(pixel_values=x).image_embeds
+
+    sys.modules["clip"].load = lambda name, device=None, **k: (ClipStandIn(hf), preprocess)
+    _install_tv_transforms()
+    tv, tvm = sys.modules["torchvision"], sys.modules["torchvision.models"]
+    tv.__version__ = "0.12.0"
+
+    class _Block(torch.nn.Module):
+        def __init__(self, *a, **k):
+            super().__init__()
+
+    class _NoInception:
+        """torchvision's inception_v3 as the reference needs it to build: any layer is an Identity, no weights are loaded."""
+
+        def __getattr__(self, name):
+            return torch.nn.Identity()
+
+        def load_state_dict(self, sd):
+            return None
+
+    tvi = ref_shims._mod("torchvision.models.inception")
+    tvi.InceptionA = tvi.InceptionC = tvi.InceptionE = _Block
+    tvm.inception, tvm.inception_v3 = tvi, (lambda *a, **k: _NoInception())
+    ref_shims._mod("torchvision.models.utils").load_state_dict_from_url = lambda *a, **k: {}
+    try:
+        import tqdm  # noqa: F401
+    except ImportError:
+        pass          # fid_score.py has its own fallback
+
+    def by_path(name, path):
+        spec = importlib.util.spec_from_file_location(name, path)
+        m = importlib.util.module_from_spec(spec)
+        sys.modules[name] = m
+        spec.loader.exec_module(m)
+        return m
+
+    by_path("inception", "/root/reference/eval_tool/fid/inception.py")
+    R = by_path("ref_fid_score", "/root/reference/eval_tool/fid/fid_score.py")
+
+    class _NP:
+        """numpy, with get_activations' hard-coded 512 feature columns replaced by the fixture tower's projection width."""
+
+        def __getattr__(self, name):
+            return getattr(np, name)
+
+        def empty(self, shape, *a, **k):
+            return np.empty((shape[0], cfg.proj) if tuple(shape[1:]) == (512,) else shape, *a, **k)
+
+    R.np = _NP()
+    data = I.build()
+    dev = torch.device("cpu")
+    model = R.InceptionV3([R.InceptionV3.BLOCK_INDEX_BY_DIM[2048]]).to(dev)
+    with tempfile.TemporaryDirectory() as tmp:
+        paths = I.write_folders(tmp, data)
+        files = [FS.list_images(p) for p in paths]
+        assert [[os.path.basename(f) for f in fl] for fl in files] == [data["dataset_names"], data["result_names"]]
+        act = [R.get_activations([__import__("pathlib").Path(f) for f in fl], model, 50, 2048, dev, 0) for fl in files]
+        stats = [R.calculate_activation_statistics([__import__("pathlib").Path(f) for f in fl], model, 50, 2048, dev, 0) for fl in files]
+        said = io.StringIO()
+        with contextlib.redirect_stdout(said):
+            fid = R.calculate_fid_given_paths(paths, 50, dev, 2048, 0)
+        x = [torch.cat([R.ImagePathDataset(fl)[i] for i in range(len(fl))]) for fl in files]          # [48, 3, 224, 224] each
+    assert act[0].shape == (48, cfg.proj) and act[0].dtype == np.float64
+    assert "singular" not in said.getvalue(), said.getvalue()
+    with contextlib.redirect_stdout(said):
+        assert float(R.calculate_frechet_distance(stats[0][0], stats[0][1], stats[1][0], stats[1][1])) == float(fid)
+    from scipy import linalg
+    root, _ = linalg.sqrtm(stats[0][1].dot(stats[1][1]), disp=False)
+    imag = float(np.abs(root.imag).max()) if np.iscomplexobj(root) else 0.0
+    conds = [float(np.linalg.cond(s)) for _, s in stats]
+    print(f"  FID {float(fid):.6f}; cond(sigma) {conds[0]:.3e} {conds[1]:.3e}; sqrtm finite {bool(np.isfinite(root).all())}, max |imag| {imag:.2e}")
+    assert np.isfinite(root).all() and imag == 0.0 and max(conds) < 1e6, "degenerate fixture"
+
+    # the same module on the same prepared tensors, in fp32 (one batch per folder, as the script ran them), float64 and bfloat16
+    f32 = [hf(pixel_values=t).image_embeds.numpy() for t in x]
+    assert all(np.array_equal(a.astype(np.float32), b) for a, b in zip(act, f32)), "get_activations must equal the module's own fp32 output"
+    hf.double()
+    f64 = [hf(pixel_values=t.double()).image_embeds.numpy() for t in x]
+    hf.bfloat16()
+    fbf = [hf(pixel_values=t.bfloat16()).image_embeds.float().numpy() for t in x]
+    e_ref = max(float(np.abs(a - b).max()) for a, b in zip(f32, f64))
+    e_bf = max(float(np.abs(a - b).max()) for a, b in zip(fbf, f64))
+    for (mu, sg), a in zip(stats, act):
+        hm, hs = FS.stats_host(a)
+        assert np.array_equal(hm, mu) and np.array_equal(hs, sg)
+    assert abs(FS.frechet_distance(stats[0][0], stats[0][1], stats[1][0], stats[1][1]) - float(fid)) <= 1e-12 * abs(float(fid))
+
+    def fid_of(fa, fb):
+        (m1, s1), (m2, s2) = FS.stats_host(fa), FS.stats_host(fb)
+        return float(FS.frechet_distance(m1, s1, m2, s2))
+
+    fid64 = fid_of(f64[0], f64[1])
+    tol = {}
+    for tag, e in (("f32", e_ref), ("bf16", e_bf)):
+        worst = 0.0
+        for k in range(8):
+            rng = np.random.default_rng(4100 + k)
+            worst = max(worst, abs(fid_of(f64[0] + rng.uniform(-4 * e, 4 * e, f64[0].shape), f64[1] + rng.uniform(-4 * e, 4 * e, f64[1].shape)) - fid64))
+        tol[tag] = 2.0 * worst
+    print(f"  e_ref_feat {e_ref:.3e}  e_ref_feat_bf16 {e_bf:.3e}  FID f64 {fid64:.6f}  fid_tol f32 {tol['f32']:.3e} bf16 {tol['bf16']:.3e}; max |feature| {np.abs(f64[0]).max():.3f}")
+
+    # ViT-B/32's own dimensions, seeded, on 4 images
+    big_cfg = P.CLIPVisionConfig(**FS.VIT_B32)
+    big_sd = FS.seeded_fid_state(big_cfg)
+    big = _hf_fid_tower(big_cfg, big_sd)
+    xb = x[0][list(I.B32_IMAGES)]
+    b32 = big(pixel_values=xb).image_embeds.numpy()
+    big.double()
+    b64 = big(pixel_values=xb.double()).image_embeds.numpy()
+    e_b32 = float(np.abs(b32 - b64).max())
+    print(f"  ViT-B/32-sized tower: e_ref {e_b32:.3e}, max |feature| {np.abs(b64).max():.3f}")
+    prep = np.stack([x[0][i].numpy() for i in I.PREP_SAMPLES])
+    save("fid", prep=prep, prep_index=np.array(I.PREP_SAMPLES), feat_f32_dataset=f32[0], feat_f32_results=f32[1], feat_f64_dataset=f64[0], feat_f64_results=f64[1],
+         e_ref_feat=np.float64(e_ref), e_ref_feat_bf16=np.float64(e_bf), mu_dataset=stats[0][0], sigma_dataset=stats[0][1], mu_results=stats[1][0],
+         sigma_results=stats[1][1], fid=np.float64(fid), fid_f64=np.float64(fid64), fid_tol_f32=np.float64(tol["f32"]), fid_tol_bf16=np.float64(tol["bf16"]),
+         b32_index=np.array(I.B32_IMAGES), b32_feat_f32=b32, b32_feat_f64=b64, b32_e_ref=np.float64(e_b32), seed=FS.SEED)
+
+
 GROUPS = dict(ddim_full=gen_ddim_full, unet_keys=gen_unet_keys, plms=gen_plms, schedule=gen_schedule, unet_ops=gen_unet_ops, unet_small=gen_unet_small, unet_full=gen_unet_full,
               ddim=gen_ddim, vae=gen_vae, arcface=gen_arcface, clip=gen_clip, e2e=gen_e2e,
-              bisenet=gen_bisenet, align=gen_align, idscore=gen_idscore, pose=gen_pose, expr=gen_expr)
+              bisenet=gen_bisenet, align=gen_align, idscore=gen_idscore, pose=gen_pose, expr=gen_expr, fid=gen_fid)
 
 if __name__ == "__main__":
     sel = sys.argv[1:] or [g for g in GROUPS if g != "ddim_full"]          # (ddim_full: 20 minutes; ask for it by name)
