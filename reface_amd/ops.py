@@ -904,6 +904,7 @@ def timestep_embedding(t, freqs, out, name="timestep_embedding"):
 def silu_f32(x, out, name="silu"):
     lib = _lib.load()
     _require_gpu(x, out)
+    assert x.dtype == torch.float32 and out.dtype == torch.float32 and x.is_contiguous() and out.is_contiguous() and x.numel() == out.numel()
     return Launch(lib.rf_silu_f32, (_p(x), _p(out), x.numel()), (x, out), name)
 
 
@@ -1188,6 +1189,7 @@ def mul_mask(x, mask, out, name="mul_mask"):
     lib = _lib.load()
     _require_gpu(x, mask, out)
     B, Cc, H, W_ = x.shape
+    assert x.dtype == torch.float32 and mask.dtype == torch.float32 and out.dtype == torch.float32
     assert x.is_contiguous() and mask.is_contiguous() and out.is_contiguous() and mask.numel() == B * H * W_
     return Launch(lib.rf_mul_mask, (_p(x), _p(mask), B, Cc, H * W_, _p(out)), (x, mask, out), name)
 
@@ -1196,6 +1198,8 @@ def gaussian_sample(moments, eps, out, *, scale, name="gaussian_sample"):
     lib = _lib.load()
     _require_gpu(moments, eps, out)
     B, C2, H, W_ = moments.shape
+    assert moments.dtype == torch.float32 and out.dtype == torch.float32 and (eps is None or eps.dtype == torch.float32)
+    assert C2 % 2 == 0 and out.shape == (B, C2 // 2, H, W_) and (eps is None or eps.shape == out.shape)
     assert moments.is_contiguous() and out.is_contiguous() and (eps is None or eps.is_contiguous())
     return Launch(lib.rf_gaussian_sample, (_p(moments), _p(eps), float(scale), _p(out), B, C2 // 2, H * W_), (moments, eps, out), name)
 
@@ -1215,6 +1219,9 @@ def channel_affine(x, a, b, out, slope=None, name="channel_affine"):
     _require_gpu(x, a, b, out, slope)
     Cc = x.shape[-1]
     M = x.numel() // Cc
+    for t in (a, b, slope):
+        assert t is None or (t.dtype == torch.float32 and t.shape == (Cc,) and t.is_contiguous())
+    assert x.dim() >= 2 and x.shape == out.shape and x.stride(-1) == 1 and out.stride(-1) == 1
     return Launch(lib.rf_channel_affine, (code(x.dtype), _p(x), x.stride(-2), _p(a), _p(b), _p(slope), code(out.dtype), _p(out),
                                           out.stride(-2), M, Cc), (x, a, b, slope, out), name)
 
@@ -1223,7 +1230,8 @@ def spatial_mean(x, out, name="spatial_mean"):
     lib = _lib.load()
     _require_gpu(x, out)
     B, H, W_, Cc = x.shape
-    assert out.dtype == torch.float32 and out.is_contiguous()
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B, Cc)
+    assert x.stride(3) == 1 and x.stride(1) == W_ * x.stride(2) and x.stride(0) == H * W_ * x.stride(2)
     return Launch(lib.rf_spatial_mean, (code(x.dtype), _p(x), B, H * W_, Cc, x.stride(2), _p(out)), (x, out), name)
 
 
@@ -1232,6 +1240,10 @@ def se_scale_add(r, s, shortcut, out, *, stride, name="se_scale_add"):
     _require_gpu(r, s, shortcut, out)
     B, Ho, Wo, Cc = r.shape
     assert r.is_contiguous() and out.is_contiguous() and s.dtype == torch.float32 and shortcut.dtype == r.dtype
+    assert s.shape == (B, Cc) and s.is_contiguous() and out.dtype == r.dtype and out.shape == r.shape
+    Bs, Hs, Ws, Cs = shortcut.shape
+    ldsc = shortcut.stride(2)
+    assert Bs == B and Cs == Cc and shortcut.stride(3) == 1 and shortcut.stride(1) == Ws * ldsc and shortcut.stride(0) == Hs * Ws * ldsc
     return Launch(lib.rf_se_scale_add, (code(r.dtype), _p(r), _p(s), _p(shortcut), shortcut.stride(2), shortcut.shape[1], shortcut.shape[2],
                                         stride, _p(out), B, Ho, Wo, Cc), (r, s, shortcut, out), name)
 
@@ -1311,7 +1323,9 @@ def clip_tokens(patch, cls, pos, out, name="clip_tokens"):
     lib = _lib.load()
     _require_gpu(patch, cls, pos, out)
     B, NP, Cc = patch.shape
-    assert patch.is_contiguous() and out.is_contiguous() and patch.dtype == out.dtype
+    assert patch.is_contiguous() and out.is_contiguous() and patch.dtype == out.dtype and out.shape == (B, NP + 1, Cc)
+    assert cls.dtype == torch.float32 and cls.shape == (Cc,) and cls.is_contiguous()
+    assert pos.dtype == torch.float32 and pos.shape == (NP + 1, Cc) and pos.is_contiguous()
     return Launch(lib.rf_clip_tokens, (code(patch.dtype), _p(patch), _p(cls), _p(pos), _p(out), B, NP, Cc), (patch, cls, pos, out), name)
 
 
@@ -1319,6 +1333,7 @@ def l2norm_rows(x, out, name="l2norm_rows"):
     lib = _lib.load()
     _require_gpu(x, out)
     assert x.dtype == torch.float32 and x.is_contiguous() and out.is_contiguous()
+    assert out.dtype == torch.float32 and x.dim() == 2 and out.shape == x.shape
     return Launch(lib.rf_l2norm_rows, (_p(x), _p(out), x.shape[0], x.shape[1]), (x, out), name)
 
 
