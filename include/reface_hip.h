@@ -558,6 +558,36 @@ int rf_expr_distance(const float* coef_res, int M, const float* coef_tgt, int N,
 int rf_fid_prep_u8(const void* images_u8, int B, int H, int W, int64_t image_stride, const int* xbounds, const int* xk, int xksize,
                    const int* ybounds, const int* yk, int yksize, int out_dtype, void* out, void* stream);
 int rf_fid_stats(const float* feat, int N, int D, double* mu, double* sigma, void* stream);
+/*
+ * The learned perceptual distance of the evaluation (eval_tool/lpips/{lpips,networks,utils}.py of the reference: LPIPS(net_type = 'alex' |
+ * 'vgg')), the passes around the AlexNet / VGG16 feature stacks (which run on rf_conv_gemm):
+ *   rf_lpips_prep_u8  : images u8 [B, H, W, 3] (image b at images + b * image_stride bytes; any H, W >= 1) -> out fp32 NHWC [B, H, W, 8]
+ *                       (16-byte aligned): x = (float32(byte) / 255 - 0.5) / 0.5 (ToTensor + Normalize(0.5, 0.5): how the reference's datasets
+ *                       bring images to [-1, 1]), then BaseNet.z_score (x - mean) / std with mean (-.030, -.088, -.188) and std
+ *                       (.458, .448, .450) (networks.py:41-51); every step rounded to fp32 in that order.  Channels 0..2; zeros in 3..7 (the
+ *                       stems' cin_pad = 8 layout).
+ *   rf_lpips_prep_f32 : x fp32 NCHW [B, 3, H, W] (contiguous) -> the same z-score and layout (the module surface takes tensors in [-1, 1]).
+ *   rf_maxpool2d      : x fp32 NHWC [B, H, W, C] (contiguous, 16-byte aligned, C a multiple of 4) -> out [B, (H - k) / 2 + 1, (W - k) / 2 + 1, C]:
+ *                       MaxPool2d(k, stride 2), k = 2 or 3, no padding, floor mode (torchvision's vgg16 / alexnet features).  H, W >= k.
+ *                       (rf_maxpool3x3s2 is the padding-1 pool of the ResNets.)
+ *   rf_lpips_layer    : fx, fy fp32 NHWC [B, HW, C] (contiguous, 16-byte aligned; C a multiple of 4, 4 <= C <= 512; B <= 65535), w fp32 [C]
+ *                       (16-byte aligned; the layer's `lin.<l>.1.weight`) -> vals[b * L + l] fp64 = mean over the HW pixels of
+ *                       sum_c w[c] (n(fx)[c] - n(fy)[c])^2 with n(f) = f / (sqrt(sum_c f^2 + 1e-16) + 1e-10) (utils.py:6-8, lpips.py:32-33).
+ *                       Each feature byte is read once; the direct form (normalise, subtract, square, weight), everything computed from
+ *                       the fp32 features in fp64 (norms, differences, sums, the mean): near-equal maps keep their small difference.  No atomics: block partials go to `scratch` (fp64, at least
+ *                       B * min(RF_LPIPS_MAX_BLOCKS, HW) entries; `scratch_doubles` is its size) and meet in a fixed order.  The blocks of a
+ *                       pair depend on HW and C only: vals[b, l] has the same bits for every B and on every run.  A pixel whose channels are
+ *                       all zero normalises to zeros; fx == fy gives exactly 0.
+ *   rf_lpips_total    : vals fp64 [B, L] -> d fp64 [B] = sum_l vals[b, l] (l ascending) and totals fp64 [2] = (sum_b d[b], b ascending; B): the
+ *                       reference's scalar is totals[0] / totals[1] (lpips.py:35).
+ */
+#define RF_LPIPS_MAX_BLOCKS 1024
+int rf_lpips_prep_u8(const void* images_u8, int B, int H, int W, int64_t image_stride, float* out, void* stream);
+int rf_lpips_prep_f32(const float* x_nchw, int B, int H, int W, float* out, void* stream);
+int rf_maxpool2d(const float* x, int B, int H, int W, int C, int k, float* out, void* stream);
+int rf_lpips_layer(const float* fx, const float* fy, int B, int64_t HW, int C, const float* w, double* scratch, int64_t scratch_doubles, double* vals,
+                   int L, int l, void* stream);
+int rf_lpips_total(const double* vals, int B, int L, double* d, double* totals, void* stream);
 /* elementwise y = silu(x) on fp32 (emb path, openaimodel.py:219) */
 int rf_silu_f32(const float* x, float* y, int64_t n, void* stream);
 

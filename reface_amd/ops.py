@@ -1177,6 +1177,65 @@ def fid_stats(feat, mu, sigma, name="fid_stats"):
     return Launch(lib.rf_fid_stats, (_p(feat), N, D, _p(mu), _p(sigma)), (feat, mu, sigma), name)
 
 
+LPIPS_MAX_BLOCKS = 1024          # RF_LPIPS_MAX_BLOCKS (include/reface_hip.h): block partials per image pair of rf_lpips_layer at the most
+
+
+def lpips_prep_u8(images_u8, out, name="lpips_prep_u8"):
+    """The LPIPS input in one launch (rf_lpips_prep_u8): images uint8 [B, H, W, 3] (packed images, any image stride, any H, W >= 1) -> out
+    fp32 NHWC [B, H, W, 8] = z_score((u8 / 255 - 0.5) / 0.5) in channels 0..2, zeros in 3..7."""
+    lib = _lib.load()
+    _require_gpu(images_u8, out)
+    B, H, W_, C3 = images_u8.shape
+    assert images_u8.dtype == torch.uint8 and C3 == 3
+    assert images_u8.stride(3) == 1 and images_u8.stride(2) == 3 and images_u8.stride(1) == W_ * 3
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B, H, W_, 8), tuple(out.shape)
+    return Launch(lib.rf_lpips_prep_u8, (_p(images_u8), B, H, W_, images_u8.stride(0) if B > 1 else H * W_ * 3, _p(out)), (images_u8, out), name)
+
+
+def lpips_prep_f32(x, out, name="lpips_prep_f32"):
+    """The same z-score and layout from fp32 NCHW [B, 3, H, W] in [-1, 1] (rf_lpips_prep_f32) -> out fp32 NHWC [B, H, W, 8]."""
+    lib = _lib.load()
+    _require_gpu(x, out)
+    B, C3, H, W_ = x.shape
+    assert x.dtype == torch.float32 and C3 == 3 and x.is_contiguous()
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B, H, W_, 8), tuple(out.shape)
+    return Launch(lib.rf_lpips_prep_f32, (_p(x), B, H, W_, _p(out)), (x, out), name)
+
+
+def maxpool2d(x, out, *, k, name="maxpool2d"):
+    """MaxPool2d(k, 2), no padding, floor mode, of fp32 [B, H, W, C] -> [B, (H-k)//2+1, (W-k)//2+1, C] (rf_maxpool2d; k = 2 or 3)."""
+    lib = _lib.load()
+    _require_gpu(x, out)
+    B, H, W_, Cc = x.shape
+    assert x.dtype == out.dtype == torch.float32 and x.is_contiguous() and out.is_contiguous()
+    assert out.shape == (B, (H - k) // 2 + 1, (W_ - k) // 2 + 1, Cc), (tuple(x.shape), k, tuple(out.shape))
+    return Launch(lib.rf_maxpool2d, (_p(x), B, H, W_, Cc, int(k), _p(out)), (x, out), name)
+
+
+def lpips_layer(fx, fy, w, scratch, vals, l, name="lpips_layer"):
+    """One LPIPS tap (rf_lpips_layer): fx, fy fp32 NHWC [B, ..., C] (contiguous), w fp32 [C] -> vals[b, l] fp64 = mean over the pixels of
+    sum_c w[c] (n(fx) - n(fy))^2.  vals: fp64 [B, L]; scratch: fp64, B * min(LPIPS_MAX_BLOCKS, pixels) entries at least."""
+    lib = _lib.load()
+    _require_gpu(fx, fy, w, scratch, vals)
+    B, Cc = fx.shape[0], fx.shape[-1]
+    HW = fx.numel() // (B * Cc)
+    assert fx.dtype == fy.dtype == w.dtype == torch.float32 and fx.shape == fy.shape and fx.is_contiguous() and fy.is_contiguous()
+    assert w.shape == (Cc,) and w.is_contiguous()
+    assert scratch.dtype == vals.dtype == torch.float64 and scratch.is_contiguous() and vals.is_contiguous() and vals.dim() == 2 and vals.shape[0] == B
+    return Launch(lib.rf_lpips_layer, (_p(fx), _p(fy), B, HW, Cc, _p(w), _p(scratch), scratch.numel(), _p(vals), vals.shape[1], int(l)),
+                  (fx, fy, w, scratch, vals), name)
+
+
+def lpips_total(vals, d, totals, name="lpips_total"):
+    """vals fp64 [B, L] -> d fp64 [B] = the layers summed in order, totals fp64 [2] = (sum of d in index order, B) (rf_lpips_total)."""
+    lib = _lib.load()
+    _require_gpu(vals, d, totals)
+    B, L = vals.shape
+    assert vals.dtype == d.dtype == totals.dtype == torch.float64 and vals.is_contiguous() and d.is_contiguous() and totals.is_contiguous()
+    assert d.shape == (B,) and totals.shape == (2,)
+    return Launch(lib.rf_lpips_total, (_p(vals), B, L, _p(d), _p(totals)), (vals, d, totals), name)
+
+
 def label_mask(labels_u8, lut256, out, *, invert, name="label_mask"):
     lib = _lib.load()
     _require_gpu(labels_u8, lut256, out)

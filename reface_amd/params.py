@@ -508,6 +508,68 @@ def recon_param_specs():
     return s
 
 
+LPIPS_CHANNELS = {"alex": (64, 192, 384, 256, 256), "vgg": (64, 128, 256, 512, 512)}          # n_channels_list (networks.py:83, 94)
+
+
+def lpips_plan(net):
+    """The feature stack of LPIPS's backbone up to its fifth tap (eval_tool/lpips/networks.py:53-63, 77-96) as a list of
+    ("conv", index, cin, cout, ksize, stride, pad) -- always followed by a ReLU --, ("pool", ksize) -- MaxPool2d(ksize, 2), no padding, floor
+    mode -- and ("tap", l).  ``index`` is the module's position in torchvision's ``features`` (the state-dict key).  The reference counts
+    modules from 1, so its target layers [2, 5, 8, 10, 12] (alex) and [4, 9, 16, 23, 30] (vgg) are the ReLUs at 0-based 1, 4, 7, 9, 11 and
+    3, 8, 15, 22, 29: relu1..relu5 of AlexNet, relu1_2, relu2_2, relu3_3, relu4_3, relu5_3 of VGG16.  The loop breaks after the fifth tap:
+    the last MaxPool of either stack never runs."""
+    if net == "alex":
+        mods = [("conv", 3, 64, 11, 4, 2), "relu", ("pool", 3), ("conv", 64, 192, 5, 1, 2), "relu", ("pool", 3), ("conv", 192, 384, 3, 1, 1), "relu",
+                ("conv", 384, 256, 3, 1, 1), "relu", ("conv", 256, 256, 3, 1, 1), "relu", ("pool", 3)]
+        targets = (2, 5, 8, 10, 12)
+    elif net == "vgg":
+        mods, cin = [], 3
+        for v in (64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512, "M"):
+            if v == "M":
+                mods.append(("pool", 2))
+            else:
+                mods += [("conv", cin, v, 3, 1, 1), "relu"]
+                cin = v
+        targets = (4, 9, 16, 23, 30)
+    elif net == "squeeze":
+        raise NotImplementedError("LPIPS net_type 'squeeze' is not implemented: no caller of the reference uses it (choose 'alex' or 'vgg')")
+    else:
+        raise NotImplementedError(f"LPIPS net_type {net!r} is unknown: 'alex' and 'vgg' are built")
+    plan, taps = [], 0
+    for i, m in enumerate(mods, 1):          # 1-based, as the reference's loop
+        if m == "relu":
+            assert plan[-1][0] == "conv"
+        elif m[0] == "conv":
+            plan.append(("conv", i - 1) + m[1:])
+        else:
+            plan.append(m)
+        if i in targets:
+            assert m == "relu", (net, i, m)
+            plan.append(("tap", taps))
+            taps += 1
+        if taps == len(targets):
+            break
+    assert tuple(p[3] for p, q in zip(plan, plan[1:]) if q[0] == "tap") == LPIPS_CHANNELS[net]
+    return plan
+
+
+def lpips_param_specs(net="alex"):
+    """State-dict keys of the reference's ``LPIPS(net_type)`` (eval_tool/lpips/lpips.py:16-27), in module order: BaseNet's ``mean`` / ``std``
+    buffers, every convolution of torchvision's ``features`` (all of them lie before the fifth tap), and the five bias-free 1x1 ``lin`` convolutions:
+    17 entries for 'alex', 33 for 'vgg'."""
+    s = OrderedDict()
+    s["net.mean"] = (1, 3, 1, 1)
+    s["net.std"] = (1, 3, 1, 1)
+    for p in lpips_plan(net):
+        if p[0] == "conv":
+            _, i, cin, cout, k, _, _ = p
+            s[f"net.layers.{i}.weight"] = (cout, cin, k, k)
+            s[f"net.layers.{i}.bias"] = (cout,)
+    for l, c in enumerate(LPIPS_CHANNELS[net]):
+        s[f"lin.{l}.1.weight"] = (1, c, 1, 1)
+    return s
+
+
 def cond_head_specs():
     """Top-level LatentDiffusion conditioning heads (ddpm.py:698-733)."""
     s = OrderedDict()

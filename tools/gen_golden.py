@@ -8,7 +8,7 @@ as small ``.npz`` fixtures under tests/golden/.  Only DATA is stored (tensors + 
 needed to regenerate the weights); no reference source is copied.
 
 Usage:  python tools/gen_golden.py [group ...]     (groups: schedule unet_ops unet_small unet_full
-                                                    ddim vae arcface clip e2e bisenet align idscore pose expr fid)
+                                                    ddim vae arcface clip e2e bisenet align idscore pose expr fid lpips)
 """
 import os
 import sys
@@ -1196,9 +1196,162 @@ def gen_fid():
          b32_index=np.array(I.B32_IMAGES), b32_feat_f32=b32, b32_feat_f64=b64, b32_e_ref=np.float64(e_b32), seed=FS.SEED)
 
 
+def _tv_feature_stacks():
+    """torchvision's ``alexnet().features`` and ``vgg16().features`` restated (torchvision is absent here, see README): the module
+    sequences of torchvision/models/alexnet.py and vgg.py (configuration "D", no batch norm), hence torchvision's state-dict indices.
+    Returned as the two constructors the reference calls (``models.alexnet(True)``, ``models.vgg16(True)``): the ``pretrained`` flag is
+    ignored -- nothing is downloaded, the weights are loaded afterwards."""
+    nn = torch.nn
+
+    class _Net(nn.Module):
+        def __init__(self, features):
+            super().__init__()
+            self.features = features
+
+    def alexnet(pretrained=False, **kw):
+        return _Net(nn.Sequential(
+            nn.Conv2d(3, 64, kernel_size=11, stride=4, padding=2), nn.ReLU(inplace=True), nn.MaxPool2d(kernel_size=3, stride=2),
+            nn.Conv2d(64, 192, kernel_size=5, padding=2), nn.ReLU(inplace=True), nn.MaxPool2d(kernel_size=3, stride=2),
+            nn.Conv2d(192, 384, kernel_size=3, padding=1), nn.ReLU(inplace=True),
+            nn.Conv2d(384, 256, kernel_size=3, padding=1), nn.ReLU(inplace=True),
+            nn.Conv2d(256, 256, kernel_size=3, padding=1), nn.ReLU(inplace=True), nn.MaxPool2d(kernel_size=3, stride=2)))
+
+    def vgg16(pretrained=False, **kw):
+        layers, cin = [], 3
+        for v in (64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512, "M"):
+            if v == "M":
+                layers.append(nn.MaxPool2d(kernel_size=2, stride=2))
+            else:
+                layers += [nn.Conv2d(cin, v, kernel_size=3, padding=1), nn.ReLU(inplace=True)]
+                cin = v
+        return _Net(nn.Sequential(*layers))
+
+    return alexnet, vgg16
+
+
+def gen_lpips():
+    """The perceptual distance (eval_tool/lpips/{lpips,networks,utils}.py): the reference's own LPIPS module -- BaseNet.forward,
+    normalize_activation, LinLayers and LPIPS.forward -- on the seeded pairs of tests/lpips_inputs.py, for 'alex' and 'vgg'.  The three files
+    are loaded by path (``eval_tool`` is a stub in ref_shims and a package of this repository; neither is the reference's).  What this
+    container lacks is restated: torchvision's two feature stacks (_tv_feature_stacks, on the stub ``torchvision.models``); the two
+    downloads are replaced: ``get_state_dict`` returns the seeded linear weights, and the whole module is then loaded strictly with
+    reface_amd.lpips.load_lpips_state("none", net).  Inputs are ToTensor + Normalize(0.5, 0.5) of the bytes, as the reference's datasets
+    prepare images.  Stored (tests/golden/lpips.npz): per case v[b, l], d[b] and the module's scalar from the module in fp32 (the reference as
+    it runs) and from the same module and inputs in float64; the normalised tap features of one 'alex' pair (float64); the folder case's
+    labels, v and d; e_ref = the largest relative |fp32 - fp64| over the v[b, l] of the ordinary pairs, e_ref_near the same over the
+    near-identical pairs.  tests/golden/lpips_keys.json holds the module's state-dict keys and shapes, in order, for both nets.  A degenerate
+    fixture is refused: every ordinary v[b, l] must exceed 1e-6, every near-identical d must be positive and below a tenth of the smallest
+    ordinary d of its case, and pairing the folder's results by position must move its value by more than 1 %."""
+    import importlib.util
+    import json
+    sys.path.insert(1, os.path.join(os.path.dirname(HERE), "tests"))
+    import lpips_inputs as I
+    from reface_amd import lpips as LP
+
+    tvm = sys.modules["torchvision.models"]
+    tvm.alexnet, tvm.vgg16 = _tv_feature_stacks()
+    names = ["eval_tool.lpips.utils", "eval_tool.lpips.networks", "eval_tool.lpips.lpips"]
+    saved = {n: sys.modules.get(n) for n in names}
+    current = {}
+
+    def load(name):
+        spec = importlib.util.spec_from_file_location(name, "/root/reference/eval_tool/lpips/%s.py" % name.rsplit(".", 1)[1])
+        m = importlib.util.module_from_spec(spec)
+        sys.modules[name] = m
+        spec.loader.exec_module(m)
+        return m
+
+    try:
+        U = load(names[0])
+        U.get_state_dict = lambda net_type="alex", version="0.1": {f"{l}.1.weight": current["sd"][f"lin.{l}.1.weight"] for l in range(LP.N_TAPS)}
+        load(names[1])
+        R = load(names[2])          # binds U.get_state_dict as patched above
+
+        def module(net, dtype):
+            current["sd"] = LP.load_lpips_state("none", net)
+            m = R.LPIPS(net_type=net).eval()
+            m.load_state_dict(current["sd"], strict=True)
+            return m.to(dtype)
+
+        def run(m, x, y):
+            """v [B, L] and the scalar, by the lines of LPIPS.forward (lpips.py:30-35)."""
+            x, y = x.to(next(m.parameters()).dtype), y.to(next(m.parameters()).dtype)
+            feat_x, feat_y = m.net(x), m.net(y)
+            diff = [(fx - fy) ** 2 for fx, fy in zip(feat_x, feat_y)]
+            res = [l(d).mean((2, 3), True) for d, l in zip(diff, m.lin)]
+            v = torch.cat(res, 1)[:, :, 0, 0]
+            scalar = m(x, y)
+            assert scalar.dim() == 0 and abs(float(scalar) - float(torch.sum(torch.cat(res, 0)) / x.shape[0])) == 0.0
+            return v.double().numpy(), float(scalar), feat_x, feat_y
+
+        keys, mods = {}, {}
+        for net in ("alex", "vgg"):
+            mods[net] = (module(net, torch.float32), module(net, torch.float64))
+            ref_sd = mods[net][0].state_dict()
+            keys[net] = [[k, list(v.shape)] for k, v in ref_sd.items()]
+            assert [k for k, _ in keys[net]] == list(P.lpips_param_specs(net)), "key order"
+        assert len(keys["alex"]) == 17 and len(keys["vgg"]) == 33, (len(keys["alex"]), len(keys["vgg"]))
+
+        def tensors(images):
+            return torch.from_numpy(np.stack([LP.prep_host(im) for im in images]))
+
+        out, e_ref, e_near = {}, 0.0, 0.0
+        for c, (net, h, w) in enumerate(I.CASES):
+            xs, ys = I.build_case(c)
+            x, y = tensors(xs), tensors(ys)
+            v32, s32, _, _ = run(mods[net][0], x, y)
+            v64, s64, fx64, fy64 = run(mods[net][1], x, y)
+            rel = np.abs(v32 - v64) / v64
+            ordinary = [k for k in range(I.PAIRS) if k != I.NEAR]
+            e_ref, e_near = max(e_ref, float(rel[ordinary].max())), max(e_near, float(rel[I.NEAR].max()))
+            d64 = LP.score_host(v64)["distances"]
+            print(f"  {I.case_name(c)}: scalar fp32 {s32:.8f} fp64 {s64:.8f}  d {np.array2string(d64, precision=6)}  "
+                  f"rel |fp32 - fp64|: ordinary {rel[ordinary].max():.2e}, near {rel[I.NEAR].max():.2e}")
+            if v64[ordinary].min() <= 1e-6 or not 0.0 < d64[I.NEAR] < 0.1 * d64[ordinary].min():
+                raise SystemExit(f"gen_lpips: degenerate fixture in {I.case_name(c)}: v {v64.tolist()}; change the seeds")
+            assert abs(LP.score_host(v64)["lpips_value"] - s64) <= 1e-12 * s64
+            n = I.case_name(c)
+            out.update({f"v_f32_{n}": v32, f"v_f64_{n}": v64, f"d_f32_{n}": LP.score_host(v32)["distances"], f"d_f64_{n}": d64,
+                        f"scalar_f32_{n}": np.float64(s32), f"scalar_f64_{n}": np.float64(s64)})
+            if c == I.FEATURE_CASE:
+                for l in range(LP.N_TAPS):
+                    out[f"nfeat_x_{l}"] = fx64[l][I.FEATURE_PAIR].numpy()
+                    out[f"nfeat_y_{l}"] = fy64[l][I.FEATURE_PAIR].numpy()
+
+        # the folder layout: a result is paired with the target at the position its label names; equal sizes run together
+        data = I.build_folders()
+        labels = data["labels"]
+        fv32, fv64, fpos = [], [], []
+        for i, l in enumerate(labels):
+            y = tensors([data["res_images"][i]])
+            x = tensors([data["tgt_images"][int(l)]])
+            fv32.append(run(mods[I.FOLDER_NET][0], x, y)[0][0])
+            fv64.append(run(mods[I.FOLDER_NET][1], x, y)[0][0])
+            fpos.append(run(mods[I.FOLDER_NET][1], tensors([data["tgt_images"][i]]), y)[0][0])          # (the sizes agree by position too)
+        fv32, fv64 = np.stack(fv32), np.stack(fv64)
+        folder = LP.score_host(fv64)
+        by_position = LP.score_host(np.stack(fpos))["lpips_value"]
+        print(f"  folders paired by position: {by_position:.8f}")
+        assert abs(by_position - folder["lpips_value"]) > 0.01 * folder["lpips_value"], "the fixture must expose a wrong pairing"
+        e_ref = max(e_ref, float((np.abs(fv32 - fv64) / fv64).max()))
+        print(f"  folders: LPIPS_value {folder['lpips_value']:.8f}  d {np.array2string(folder['distances'], precision=6)}")
+        print(f"  e_ref {e_ref:.3e}  e_ref_near {e_near:.3e}")
+    finally:
+        for n, m in saved.items():
+            if m is None:
+                sys.modules.pop(n, None)
+            else:
+                sys.modules[n] = m
+    path = os.path.join(OUT, "lpips_keys.json")
+    json.dump(keys, open(path, "w"), separators=(",", ":"))
+    print(f"  wrote {path}  ({os.path.getsize(path)/1024:.1f} KiB)")
+    save("lpips", labels=labels, folder_v_f32=fv32, folder_v_f64=fv64, folder_d_f64=folder["distances"], folder_value_f64=np.float64(folder["lpips_value"]),
+         folder_value_f32=np.float64(LP.score_host(fv32)["lpips_value"]), e_ref=np.float64(e_ref), e_ref_near=np.float64(e_near), seed=LP.SEED, **out)
+
+
 GROUPS = dict(ddim_full=gen_ddim_full, unet_keys=gen_unet_keys, plms=gen_plms, schedule=gen_schedule, unet_ops=gen_unet_ops, unet_small=gen_unet_small, unet_full=gen_unet_full,
               ddim=gen_ddim, vae=gen_vae, arcface=gen_arcface, clip=gen_clip, e2e=gen_e2e,
-              bisenet=gen_bisenet, align=gen_align, idscore=gen_idscore, pose=gen_pose, expr=gen_expr, fid=gen_fid)
+              bisenet=gen_bisenet, align=gen_align, idscore=gen_idscore, pose=gen_pose, expr=gen_expr, fid=gen_fid, lpips=gen_lpips)
 
 if __name__ == "__main__":
     sel = sys.argv[1:] or [g for g in GROUPS if g != "ddim_full"]          # (ddim_full: 20 minutes; ask for it by name)
