@@ -159,6 +159,13 @@ int rf_conv_gemm_plan(const rf_conv_gemm_desc* d, int32_t* bm, int32_t* bn, int3
  * epilogue form (1 = direct register -> global, 0 = staged), flags: bit 0 = split-K through fragment slabs, bit 1 = the call runs as TWO GEMM
  * kernels (a 256-wide launch whose last round of tiles is 20-60 % full is split along N; the query then also validates the second part)}. */
 int rf_conv_gemm_plan2(const rf_conv_gemm_desc* d, int32_t* info8);
+/* The same query with everything that names the kernels of the launch: info24[0..7] = rf_conv_gemm_plan2's words, then [8] waves per block (4 | 8),
+ * [9] LDS stages of the main loop (2, or 4 for the ring of the 128 x 160 tile), [10] 1 = row-extended A tiles (korder 2), [11] 1 = direct-to-LDS main
+ * loop (0: operands go through registers), [12] 1 = convolution addressing (0: plain GEMM), [13] LayerNorm role (0 none, 1 producer, 2 consumer),
+ * [14] pm, [15] pn (the tile order inside an XCD's run: patches of pm x pn tiles), [16] reduce pass of split-K (0 none, 1 stripes of 8 rows,
+ * 2 stripes of 32 rows, 3 fragment slabs), [17] [18] [19] BM, BN and waves of the SECOND kernel of a two-kernel N split (0 otherwise), [20] tile rows
+ * and [21] tile columns of the grid, [22] columns of the first kernel of a two-kernel split, [23] epilogue form of its second kernel.  No launch. */
+int rf_conv_gemm_plan3(const rf_conv_gemm_desc* d, int32_t* info24);
 
 /* Fused transformer feed-forward at C = 320 (the 64x64 level):  out = (GEGLU(x W1^T + b1)) W2^T + b2 + residual, bf16 in / out, fp32
  * accumulate, GELU on the 16-bit modes' sigmoid form (degree-5 argument, <= 2.6e-5 from the erf form: csrc/common.h).  The [M, 4C] hidden tensor stays in registers (tokens on lanes, see ffn.hip).

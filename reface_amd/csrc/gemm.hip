@@ -63,7 +63,8 @@ struct GemmParams {
     int gn_rows;
     double* gn_part[2];
     int gn_cpg[2], gn_coff[2], gn_slot[2], gn_nch[2];
-    int* plan;       // host only: rf_conv_gemm_plan / rf_conv_gemm_plan2 (no launch): {stat rows, stat cols, splitk, BM, BN, 32 TN, epilogue form, frag slabs}
+    int* plan;       // host only: rf_conv_gemm_plan / _plan2 / _plan3 (no launch), RF_PLAN_WORDS ints: {stat rows, stat cols, splitk, BM, BN, 32 TN, epilogue form,
+                     // frag slabs, then rf_conv_gemm_plan3's words 8-23 (include/reface_hip.h)}
     int epi2_ok;     // host only: operand alignment / feature set allow the direct (register -> global) epilogue
     const float* wscale;   // W8 kernels: per-output-channel power-of-two scale of the fp8 (e4m3fn) weights
     void* oscale;          // A8 kernels with GEGLU: `out` receives e4m3fn bytes (pitch ldo BYTES) and oscale one E8M0 code per (row, 32 output columns)
@@ -1708,6 +1709,7 @@ __global__ __launch_bounds__(64 * TN) void splitk_reduce_frag_kernel(const GemmP
 #ifdef RF_KERNEL_ONLY          // (diagnostics: tools/kernel_regs.sh compiles single instantiations of the kernels above)
 }  // namespace rf
 #else
+constexpr int RF_PLAN_WORDS = 24;          // ints behind GemmParams::plan (rf_conv_gemm_plan3's info24)
 // Split-K factor for a launch of `tiles` output tiles, by a two-term cost model: GEMM time at ~600 TFLOP/s stretched by the
 // fraction of the 256 CUs left idle, plus the fp32 partial-sum traffic (write + re-read of sk * M * N floats at ~4 TB/s).
 static int pick_splitk(const rf_conv_gemm_desc* d, const GemmParams& p, long long tiles, int bk) {
@@ -1835,9 +1837,17 @@ static int launch_cfg(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hipS
     RF_CHECK(p.ups != 2 || (p.splitk == 1 && (p.Hin * p.Win) % BM == 0),
              "rf_conv_gemm: ups 2 needs Hin * Win = %d to be a multiple of the %d-row tile (a tile inside one phase of one sample) and no split-K (this launch: %d)",
              p.Hin * p.Win, BM, p.splitk);
+    // (the ring of four stages: see the launch below; decided here so that rf_conv_gemm_plan3 reports it)
+    const bool deep = DEEP_OK && p.glds && !p.x3 && !hx && (long long)p.tiles_m * p.tiles_n * d->batch * p.splitk <= 256;
     if (p.plan) {
         p.plan[0] = st_rows; p.plan[1] = st_cols; p.plan[2] = p.splitk; p.plan[3] = BM; p.plan[4] = BN; p.plan[5] = 32 * TN;
         p.plan[6] = direct ? 1 : 0; p.plan[7] = frag ? 1 : 0;
+        // rf_conv_gemm_plan3: the instantiation and the grid order behind those words
+        p.plan[8] = WM * WN; p.plan[9] = deep ? NSTD : 2; p.plan[10] = hx ? 1 : 0; p.plan[11] = p.glds ? 1 : 0; p.plan[12] = conv ? 1 : 0;
+        p.plan[13] = p.ln_in ? 2 : (p.ln_out ? 1 : 0); p.plan[14] = p.pm; p.plan[15] = p.pn;
+        p.plan[16] = p.splitk > 1 ? (frag ? 3 : (skr == 8 ? 1 : 2)) : 0;
+        p.plan[17] = p.plan[18] = p.plan[19] = 0;          // (the tail of a two-kernel split: launch_typed)
+        p.plan[20] = p.tiles_m; p.plan[21] = p.tiles_n; p.plan[22] = p.plan[23] = 0;
         return 0;
     }
     if (p.gn_rows > 0) {
@@ -1879,7 +1889,6 @@ static int launch_cfg(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hipS
     // (tools/archive/exp_r03_10.sh: 921.7 -> 913.5 ms, same box, two runs each).  Forcing the 8x8 level (M = 1024) onto this tile + ring: neutral for the
     // 3x3 convs, +0.9 % for its small projections.
     constexpr int smem_deep = NSTD * (BM + BN) * 128 > smem ? NSTD * (BM + BN) * 128 : smem;
-    const bool deep = DEEP_OK && p.glds && !p.x3 && !hx && (long long)grid.x * grid.y * grid.z <= 256;
     if constexpr (A8) {            // fp8 activations: direct-to-LDS kernels only, staged or direct epilogue
         if (conv) { if (esel == 1) RF_LAUNCH_VARIANT(true, true, 1) else RF_LAUNCH_VARIANT(true, true, 0) }
         else { if (esel == 1) RF_LAUNCH_VARIANT(false, true, 1) else RF_LAUNCH_VARIANT(false, true, 0) }
@@ -2001,10 +2010,13 @@ static int launch_typed(const rf_conv_gemm_desc* d, GemmParams& p, bool conv, hi
                         // a plan query reports the whole-round tiling of the first part -- but BOTH parts must be launchable (a LayerNorm consumer
                         // needs the direct epilogue in the tail too): the tail's plan is validated here, not at the first replay.  Bit 1 of the
                         // eighth plan word says that the call runs as two GEMM kernels.
-                        int tail_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                        int tail_plan[RF_PLAN_WORDS] = {0};
                         q2.plan = tail_plan;
                         const int rc2 = launch_typed<T, TO, W8>(d, q2, conv, st);
-                        if (rc2 == 0) p.plan[7] |= 2;
+                        if (rc2 == 0) {
+                            p.plan[7] |= 2;
+                            p.plan[17] = tail_plan[3]; p.plan[18] = tail_plan[4]; p.plan[19] = tail_plan[8]; p.plan[22] = n1; p.plan[23] = tail_plan[6];
+                        }
                         return rc2;
                     }
                     return launch_typed<T, TO, W8>(d, q2, conv, st);
@@ -2265,7 +2277,7 @@ extern "C" int rf_quantize_fp8_rows(const float* w, int N, int K, int ldq, void*
 extern "C" int rf_conv_gemm_plan(const rf_conv_gemm_desc* d, int32_t* bm, int32_t* bn, int32_t* splitk) {
     using namespace rf;
     RF_CHECK(bm && bn && splitk, "rf_conv_gemm_plan: null output");
-    int plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int plan[RF_PLAN_WORDS] = {0};
     const int rc = conv_gemm_impl(d, nullptr, plan);
     *bm = plan[0]; *bn = plan[1]; *splitk = plan[2];
     return rc;
@@ -2274,9 +2286,18 @@ extern "C" int rf_conv_gemm_plan(const rf_conv_gemm_desc* d, int32_t* bm, int32_
 extern "C" int rf_conv_gemm_plan2(const rf_conv_gemm_desc* d, int32_t* info8) {
     using namespace rf;
     RF_CHECK(info8, "rf_conv_gemm_plan2: null output");
-    int plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int plan[RF_PLAN_WORDS] = {0};
     const int rc = conv_gemm_impl(d, nullptr, plan);
     for (int i = 0; i < 8; ++i) info8[i] = plan[i];
+    return rc;
+}
+
+extern "C" int rf_conv_gemm_plan3(const rf_conv_gemm_desc* d, int32_t* info24) {
+    using namespace rf;
+    RF_CHECK(info24, "rf_conv_gemm_plan3: null output");
+    int plan[RF_PLAN_WORDS] = {0};
+    const int rc = conv_gemm_impl(d, nullptr, plan);
+    for (int i = 0; i < RF_PLAN_WORDS; ++i) info24[i] = plan[i];
     return rc;
 }
 

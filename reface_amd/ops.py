@@ -677,6 +677,25 @@ def gemm_plan2(launch):
     return pl
 
 
+REDUCE_KINDS = ("none", "stripe8", "stripe32", "frag")
+
+
+def gemm_plan3(launch):
+    """Everything that names the kernels of a prepared rf_conv_gemm launch (rf_conv_gemm_plan3, no launch): gemm_plan2's dict plus waves (4 | 8), stages
+    (2, or 4 for the ring), hx, glds, conv, ln_role (0 none, 1 producer, 2 consumer), pm, pn, reduce (one of REDUCE_KINDS), tiles_m, tiles_n and, for a
+    two-kernel N split, tail = (BM, BN, waves, direct) of the second kernel and split_n = the columns of the first (else None / 0)."""
+    lib = _lib.load()
+    info = (C.c_int32 * 24)()
+    _lib.check(lib.rf_conv_gemm_plan3(C.byref(launch.keep[0]), info), launch.name + ".plan3")
+    v = [int(x) for x in info]
+    pl = dict(zip(("stat_rows", "stat_cols", "splitk", "bm", "bn", "wave_cols", "direct", "frag"), v[:8]))
+    pl["gemm_kernels"] = 2 if pl["frag"] & 2 else 1
+    pl["frag"] &= 1
+    pl.update(waves=v[8], stages=v[9], hx=v[10], glds=v[11], conv=v[12], ln_role=v[13], pm=v[14], pn=v[15], reduce=REDUCE_KINDS[v[16]],
+              tiles_m=v[20], tiles_n=v[21], tail=((v[17], v[18], v[19], v[23]) if pl["gemm_kernels"] == 2 else None), split_n=v[22])
+    return pl
+
+
 def fold_layernorm_linear(w, gamma, beta, bias, dtype):
     """LayerNorm folded into the Linear behind it, the consumer half of rf_conv_gemm's ln_* fields:
         (xhat * gamma + beta) W^T + b  =  rstd (x W'^T - mean u) + b'      with  W' = W diag(gamma),  u[n] = sum_k W'[n, k],  b' = b + W beta.

@@ -194,10 +194,9 @@ def test_groupnorm_stats_fused_into_gemm(dt, c0, c1, hw, B, kin):
         l = ops.conv2d(xin, w.reshape(c, kin), out, bias, ksize=1, pad=(0, 0), residual=res, name=f"prod{i}")
         prods.append((l, 0, B * hw * hw, off, c))
     fused = ops.fuse_groupnorm_stats(cat, prods)
-    bm, bn, sk = ops.gemm_plan(prods[0][0])
-    if (hw * hw) % bm:
-        assert fused is None
-        pytest.skip(f"plan bm={bm} splitk={sk} cannot fuse at this size")
+    for l_, *_ in prods:          # the plan every producer is here for: a statistics tile that divides the sample (a retune that breaks it fails here by name)
+        pl = ops.gemm_plan3(l_)
+        assert (hw * hw) % pl["stat_rows"] == 0, f"{l_.name}: the fused-statistics case lost its plan (sample of {hw * hw} rows): {pl}"
     assert fused is not None
     second = None
     if c1:      # the skip half alone is a second consumer (different channels per group)
@@ -406,13 +405,14 @@ def test_conv_channel_chunk_major_k(dt, stride, ups, Ci):
     check(out, ref, dt)
 
 
-@pytest.mark.parametrize("B,hw,Ci,Co", [(2, 32, 128, 320), (16, 8, 1280, 1280), (4, 16, 640, 1280), (2, 64, 320, 320), (16, 64, 320, 320), (3, 8, 128, 320),
-                                        (16, 32, 640, 640), (1, 16, 64, 64), (5, 16, 1280, 640)])
+@pytest.mark.parametrize("B,hw,Ci,Co", [(2, 32, 128, 256), (4, 16, 1280, 1280), (4, 16, 640, 1280), (2, 64, 320, 320), (16, 64, 320, 320), (3, 16, 128, 256),
+                                        (16, 32, 640, 640), (1, 16, 64, 64), (5, 16, 1280, 640)])          # (every shape takes korder 2: Wout >= 16, no 4-stage ring)
 @pytest.mark.parametrize("dt", H16)
 def test_conv_row_extended_a_tiles(B, hw, Ci, Co, dt):
     """rf_conv_gemm korder 2 (gemm.hip HX, round 4): 3x3 stride-1 convolutions with the K order (filter row, channel chunk, filter column) -- the
     three horizontal taps of a (row, chunk) share ONE row-extended A tile (every image row of the output tile + a halo pixel on each side).
-    Image borders (zero halo, top / bottom rows), tiles spanning several samples (8x8: 128-row tile = 2 samples), ragged M, split-K, and the
+    Image borders (zero halo, top / bottom rows), several image rows and whole samples per tile, split-K (square images of Wout >= 16 have
+    at least 256 rows a sample: a tile that CROSSES a sample boundary, and a ragged M, are the 4 x 16 cases of tests/test_gemm_exact_gpu.py), and the
     epilogue's bias / per-sample vector / residual / fused GroupNorm statistics -- against F.conv2d on the bf16-rounded operands, and bit-equal
     to the tap-major launch of the same layer where the summation order per accumulator is the same K-tile sequence permuted (checked to 2 ulps)."""
     x, xr = q(rnd((B, hw, hw, Ci), 160) * 0.5, dt)
@@ -422,11 +422,8 @@ def test_conv_row_extended_a_tiles(B, hw, Ci, Co, dt):
     res, rr = q(rnd((B, hw, hw, Co), 164), dt)
     out = torch.empty((B, hw, hw, Co), dtype=dt, device=DEV)
     l = ops.conv2d(x, ops.pack_conv_weight(w, dt, korder=2).to(DEV), out, b.to(DEV), rowvec=rv.to(DEV), residual=res, korder=2)
-    try:
-        pl = ops.gemm_plan2(l)
-    except Exception as e:
-        pytest.skip(f"this launch's tile cannot take korder 2: {e}")
-    assert pl["bm"] % hw == 0, pl
+    pl = ops.gemm_plan3(l)          # (raises when the launch's tile cannot take korder 2: the case then fails, it does not skip)
+    assert pl["hx"] == 1 and pl["bm"] % hw == 0, f"the row-extended case B={B} {hw}x{hw} {Ci}->{Co} lost its plan: {pl}"
     fused = ops.fuse_groupnorm_stats(out, [(l, 0, B * hw * hw, 0, Co)])
     l()
     out0 = torch.empty_like(out)
@@ -849,7 +846,7 @@ def test_ffn_block_with_out_projection_in_front(B, hw, pair, dt):
 
 
 @pytest.mark.parametrize("M,K0,Cc,N,geglu,res", [(4096, 320, 320, 960, False, False), (65536, 320, 320, 960, False, True), (16384, 640, 640, 5120, True, True),
-                                                  (4096, 1280, 1280, 3840, False, True), (1000, 320, 320, 640, True, False),
+                                                  (4096, 1280, 1280, 3840, False, True), (3000, 320, 320, 2048, True, False),
                                                   (4096, 1280, 1280, 10240, True, True)])          # (the consumer is split along N: 2.5 rounds of 256 x 256 tiles)
 @pytest.mark.parametrize("dt", H16)
 def test_layernorm_folded_around_gemms(M, K0, Cc, N, geglu, res, dt):
@@ -875,14 +872,10 @@ def test_layernorm_folded_around_gemms(M, K0, Cc, N, geglu, res, dt):
     out = torch.empty((M, N // 2 if geglu else N), dtype=dt, device=DEV)
     cons = ops.linear(y, w2.to(DEV), out, b2.to(DEV), act=act, ln_u=u2.to(DEV), name="consumer")
     stats = ops.layernorm_fold([(l_prod, 0, M)], cons, eps=1e-5, C_=Cc)
-    pl = ops.gemm_plan2(l_prod)
-    if stats is None:
-        # the fold is refused when either launch has no direct epilogue (small grids take the 4-wave 128x128 tile): the caller keeps the pass
-        cons.keep[0].ln_u = None
-        plc = ops.gemm_plan2(cons)
-        assert not pl["direct"] or pl["splitk"] != 1 or Cc % pl["wave_cols"] or not plc["direct"] or plc["splitk"] != 1, (pl, plc)
-        assert l_prod.keep[0].ln_stats_out is None and l_prod.keep[0].ln_out_parts == 0
-        pytest.skip(f"these plans cannot carry the fold: producer {pl}, consumer {plc}")
+    # (the fold is refused when either launch has no direct epilogue -- small grids take the 4-wave 128x128 tile: every shape here is chosen to carry it)
+    assert stats is not None, f"the LayerNorm-fold case M={M} lost its plan: producer {ops.gemm_plan3(l_prod)}, consumer {ops.gemm_plan2(cons)}"
+    pl, plc = ops.gemm_plan3(l_prod), ops.gemm_plan3(cons)
+    assert pl["ln_role"] == 1 and plc["ln_role"] == 2 and pl["direct"] and plc["direct"], (pl, plc)
     assert stats.shape == (M, Cc // pl["wave_cols"], 2)
     l_prod()
     cons()
@@ -911,6 +904,23 @@ def test_layernorm_folded_around_gemms(M, K0, Cc, N, geglu, res, dt):
     print(f"LayerNorm fold M={M} C={Cc} N={N} geglu={geglu}: folded vs LayerNorm pass + GEMM max |d| = {dmax:.3e} (|out| max {ref.abs().max().item():.2f}), "
           f"producer tile {pl['bm']}x{pl['bn']} stripe {wc}")
     assert dmax <= 8 * STEP[dt] * max(1.0, ref.abs().max().item())
+
+
+@pytest.mark.parametrize("dt", H16)
+def test_layernorm_fold_refused_leaves_the_launches_plain(dt):
+    """A consumer without a direct epilogue (GEGLU at N = 640 only gets the 4-wave 128x128 tile) cannot carry the fold: layernorm_fold returns
+    None and hands the producer back as a plain launch -- the caller keeps the rf_layernorm pass.  Plans only, nothing is launched."""
+    M, K0, Cc, N = 1000, 320, 320, 640
+    y = torch.empty((M, Cc), dtype=dt, device=DEV)
+    l_prod = ops.linear(torch.empty((M, K0), dtype=dt, device=DEV), torch.empty((Cc, K0), dtype=dt, device=DEV), y, torch.zeros((Cc,), device=DEV), name="producer")
+    cons = ops.linear(y, torch.empty((N, Cc), dtype=dt, device=DEV), torch.empty((M, N // 2), dtype=dt, device=DEV), torch.zeros((N,), device=DEV),
+                      act=ops.ACT_GEGLU, ln_u=torch.zeros((N,), device=DEV), name="consumer")
+    assert ops.layernorm_fold([(l_prod, 0, M)], cons, eps=1e-5, C_=Cc) is None
+    assert l_prod.keep[0].ln_stats_out is None and l_prod.keep[0].ln_out_parts == 0
+    assert cons.keep[0].ln_stats_in is None and cons.keep[0].ln_in_parts == 0
+    cons.keep[0].ln_u = None
+    pl, plc = ops.gemm_plan3(l_prod), ops.gemm_plan3(cons)
+    assert pl["ln_role"] == 0 and plc["ln_role"] == 0 and not plc["direct"] and plc["waves"] == 4, (pl, plc)          # the reason for the refusal
 
 
 # ------------------------------------------------------------------------------------------------ split-bf16 (RF_BF16X3) operands
