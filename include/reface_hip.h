@@ -316,6 +316,12 @@ int rf_layernorm(int dtype, const void* x, int M, int C, int ldx, const float* g
 int rf_attention(int dtype, const void* q, const void* k, const void* v, void* out,
                  int B, int heads, int d, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo,
                  int64_t sq, int64_t sk, int64_t sv, int64_t so, float scale, void* stream);
+/* The launch plan rf_attention takes for these sizes, as a host-only query (no pointers, no launch, no device needed; the decision is the one
+ * rf_attention itself reads).  info12 = { kernel family (0 generic, 1 x3 = split-bf16 pairs, 2 dma = the in-wave pipelined LDS-DMA kernel),
+ * storage dtype (RF_F32 for RF_BF16X3), D, 32-query blocks per wave, keys per LDS stage, waves per block, LDS stages (1 | 2; the ring depth
+ * 3 | 7 for dma), softmax denominator accumulated by the MFMA (0 | 1), queries per block, grid blocks, dynamic LDS bytes, grid % 8 }.
+ * A head dim that is not instantiated returns rf_attention's own error. */
+int rf_attention_plan(int dtype, int B, int heads, int d, int Nq, int Nk, int32_t* info12);
 
 /* fp8 activation producers of the fp8 x fp8 GEMM path (rf_conv_gemm_desc.ascale): bf16 in -> e4m3fn bytes q [rows][ldq] + one E8M0 scale byte per
  * (row, 32-channel block), scale [rows][lds]; the scale is the smallest power of two that brings the block's |max| under 448, values are

@@ -53,6 +53,15 @@ struct AttnParams {
     int nqb;          // q-blocks (of 128 queries) per (batch, head)
 };
 
+// one LDS stage of attention_kernel (esize = bytes per element) / attention_x3_kernel, and the whole dynamic LDS of attention_dma_kernel
+constexpr int attn_tile_bytes(int esize, int D, int KT) {
+    return KT * (((D + 32 / esize - 1) / (32 / esize)) * 32 + 16) + ((D + 31) / 32) * 32 * (KT * esize + 16);
+}
+constexpr int attn_x3_tile_bytes(int D, int KT) { return 2 * attn_tile_bytes(2, D, KT); }          // two bf16 images (hi, lo) per operand
+constexpr int attn_stages(int tile_bytes) { return 2 * tile_bytes <= 160 * 1024 ? 2 : 1; }
+constexpr int attn_dma_ring(int KT) { return KT == 64 ? 7 : 3; }
+constexpr int attn_dma_lds(int D, int KT) { return attn_dma_ring(KT) * (2 * KT * D * 2) + (KT - 8) * D * 2 + 128; }          // stages + the run of ones
+
 constexpr int KV_SUB = 64;          // keys per softmax / MFMA pass (the S^T accumulators of one pass: two 32-key blocks)
 
 // position of key j (0..15) inside its 16-key group in the V^T LDS row, such that lane-half h
@@ -103,6 +112,7 @@ __global__ __launch_bounds__(NW * 64, (QB == 2 && NW == 4) ? 2 : 1) void attenti
     constexpr int QW = 32 * QB;                       // queries per wave
     constexpr int TILE_BYTES = KV_TILE * KROW + DVB * 32 * VROW;      // one stage: K [64][KROW] + V^T [DVB*32][VROW]
     constexpr int NS = (2 * TILE_BYTES <= 160 * 1024) ? 2 : 1;        // double-buffer when it fits (fp32 d=160 does not)
+    static_assert(TILE_BYTES == attn_tile_bytes((int)sizeof(T), D, KV_TILE) && NS == attn_stages(TILE_BYTES), "the launch plan's LDS size is this layout's");
     // When D leaves a spare (zero-pad) row in the V^T tile, that row is set to all ones: the P V MFMA then also produces
     // the softmax denominator sum_k P[k, q] (row D of O^T) and the 32 per-tile VALU adds per lane disappear.
     constexpr bool ONES = (D % 32) != 0;
@@ -393,6 +403,7 @@ __global__ __launch_bounds__(256, 1) void attention_x3_kernel(const AttnParams p
     constexpr int K_IMG = KV_TILE * KROW, V_IMG = DVB * 32 * VROW;
     constexpr int TILE_BYTES = 2 * (K_IMG + V_IMG);          // one stage: K hi, K lo, V^T hi, V^T lo
     constexpr int NS = (2 * TILE_BYTES <= 160 * 1024) ? 2 : 1;
+    static_assert(TILE_BYTES == attn_x3_tile_bytes(D, KV_TILE) && NS == attn_stages(TILE_BYTES), "the launch plan's LDS size is this layout's");
     constexpr bool ONES = (D % 32) != 0;
     constexpr int L_I = D / 32, L_R = ((D % 32) / 8) * 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -635,32 +646,43 @@ __global__ __launch_bounds__(256, 1) void attention_x3_kernel(const AttnParams p
     }
 }
 
+// ---- the launch plan: decided ONCE (attn_decide, below the kernels), read by the launch and by rf_attention_plan ----
+enum { ATTN_GENERIC = 0, ATTN_X3 = 1, ATTN_DMA = 2 };
+struct AttnPlan {
+    int family, storage, D, QB, keys, waves, stages, ones, qpb, grid, lds;
+};
+// a launcher whose template arguments disagree with the plan it was handed would run a kernel the plan does not describe
+#define RF_ATTN_PLAN_CHECK(pl, grid_, smem_)                                                                                     \
+    RF_CHECK((pl).grid == (int)(grid_) && (pl).lds == (int)(smem_), "rf_attention: launch (grid %d, %d B of LDS) is not the plan's (%d, %d)", \
+             (int)(grid_), (int)(smem_), (pl).grid, (pl).lds)
+
 template <int D>
-static int launch_attn_x3(const AttnParams& p, int B, hipStream_t st) {
-    constexpr int KV_TILE = 64, STEPS = (D + 15) / 16, DVB = (D + 31) / 32;
-    constexpr int tile_bytes = 2 * (KV_TILE * (STEPS * 32 + 16) + DVB * 32 * (KV_TILE * 2 + 16));
-    constexpr int smem = (2 * tile_bytes <= 160 * 1024 ? 2 : 1) * tile_bytes;
+static int launch_attn_x3(const AttnPlan& pl, const AttnParams& p, int B, hipStream_t st) {
+    constexpr int KV_TILE = 64;
+    constexpr int tile_bytes = attn_x3_tile_bytes(D, KV_TILE);
+    constexpr int smem = attn_stages(tile_bytes) * tile_bytes;
     auto k = attention_x3_kernel<D, KV_TILE>;
-    RF_RAISE_LDS(k, smem, "rf_attention");
     AttnParams pp = p;
     pp.nqb = (p.Nq + 127) / 128;
+    RF_ATTN_PLAN_CHECK(pl, pp.nqb * B * p.heads, smem);
+    RF_RAISE_LDS(k, smem, "rf_attention");
     hipLaunchKernelGGL(k, dim3(pp.nqb * B * p.heads), dim3(256), smem, st, pp);
     RF_LAUNCH_CHECK("rf_attention");
     return 0;
 }
 
-static int dispatch_attn_x3(const AttnParams& p, int B, hipStream_t st) {
-    switch (p.d) {
-        case 40: return launch_attn_x3<40>(p, B, st);
-        case 64: return launch_attn_x3<64>(p, B, st);
-        case 80: return launch_attn_x3<80>(p, B, st);
-        case 160: return launch_attn_x3<160>(p, B, st);
-        case 8: return launch_attn_x3<8>(p, B, st);
-        case 16: return launch_attn_x3<16>(p, B, st);
-        case 32: return launch_attn_x3<32>(p, B, st);
+static int dispatch_attn_x3(const AttnPlan& pl, const AttnParams& p, int B, hipStream_t st) {
+    switch (pl.D) {
+        case 40: return launch_attn_x3<40>(pl, p, B, st);
+        case 64: return launch_attn_x3<64>(pl, p, B, st);
+        case 80: return launch_attn_x3<80>(pl, p, B, st);
+        case 160: return launch_attn_x3<160>(pl, p, B, st);
+        case 8: return launch_attn_x3<8>(pl, p, B, st);
+        case 16: return launch_attn_x3<16>(pl, p, B, st);
+        case 32: return launch_attn_x3<32>(pl, p, B, st);
         default: break;
     }
-    set_error("rf_attention: head dim %d not instantiated (have 8,16,32,40,64,80,160)", p.d);
+    set_error("rf_attention: head dim %d not instantiated (have 8,16,32,40,64,80,160)", pl.D);
     return 1;
 }
 
@@ -717,6 +739,7 @@ __global__ __launch_bounds__(256, (D < 48 ? 2 : 1)) void attention_dma_kernel(co
     constexpr int VPR = D / 8, KROW = D * 2;
     constexpr int K_BYTES = KT * KROW, STAGE = 2 * K_BYTES;
     constexpr int ONES_OFF = NSTG * STAGE, ONES_BYTES = (KT - 8) * KROW + 128;     // a run of bf16 ones (see the V^T fragments below)
+    static_assert(NSTG == attn_dma_ring(KT) && ONES_OFF + ONES_BYTES == attn_dma_lds(D, KT), "the launch plan's ring and LDS size are this layout's");
     constexpr int PIECES = K_BYTES / 1024;              // one-KiB DMA pieces per operand tile
     static_assert(K_BYTES % 1024 == 0 && (NU == 2 || NU == 4), "whole DMA pieces; two or four units per tile");
     constexpr int NP = 2 * PIECES, SLOTS = (NP + 3) / 4;          // pieces of a tile (K then V, contiguous in the stage), per wave
@@ -1035,74 +1058,114 @@ __global__ __launch_bounds__(256, (D < 48 ? 2 : 1)) void attention_dma_kernel(co
 }
 
 template <typename T, int D, int KT>
-static int launch_attn_dma(const AttnParams& p, int B, hipStream_t st) {
-    constexpr int smem = (KT == 64 ? 7 : 3) * (2 * KT * D * 2) + (KT - 8) * D * 2 + 128;      // stages + the run of ones
+static int launch_attn_dma(const AttnPlan& pl, const AttnParams& p, int B, hipStream_t st) {
+    constexpr int smem = attn_dma_lds(D, KT);
     auto k = attention_dma_kernel<T, D, KT>;
-    RF_RAISE_LDS(k, smem, "rf_attention");
     AttnParams pp = p;
     pp.nqb = (p.Nq + 255) / 256;
+    RF_ATTN_PLAN_CHECK(pl, pp.nqb * B * p.heads, smem);
+    RF_RAISE_LDS(k, smem, "rf_attention");
     hipLaunchKernelGGL(k, dim3(pp.nqb * B * p.heads), dim3(256), smem, st, pp);
     RF_LAUNCH_CHECK("rf_attention");
     return 0;
 }
 
 template <typename T, int D, int QB, int KV_TILE = 64, int NW = 4>
-static int launch_attn_qb(const AttnParams& p, int B, hipStream_t st) {
-    constexpr int VEC = elem<T>::VEC, KSTEP = 2 * VEC, STEPS = (D + KSTEP - 1) / KSTEP, DVB = (D + 31) / 32;
-    constexpr int KROW = STEPS * 32 + 16;
-    constexpr int VROW = KV_TILE * (int)sizeof(T) + 16;
-    constexpr int tile_bytes = KV_TILE * KROW + DVB * 32 * VROW;
-    constexpr int smem = (2 * tile_bytes <= 160 * 1024 ? 2 : 1) * tile_bytes;
+static int launch_attn_qb(const AttnPlan& pl, const AttnParams& p, int B, hipStream_t st) {
+    constexpr int tile_bytes = attn_tile_bytes((int)sizeof(T), D, KV_TILE);
+    constexpr int smem = attn_stages(tile_bytes) * tile_bytes;
     auto k = attention_kernel<T, D, QB, KV_TILE, NW>;
-    RF_RAISE_LDS(k, smem, "rf_attention");
     AttnParams pp = p;
     pp.nqb = (p.Nq + 32 * NW * QB - 1) / (32 * NW * QB);
     dim3 grid(pp.nqb * B * p.heads);
+    RF_ATTN_PLAN_CHECK(pl, grid.x, smem);
+    RF_RAISE_LDS(k, smem, "rf_attention");
     hipLaunchKernelGGL(k, grid, dim3(NW * 64), smem, st, pp);
     RF_LAUNCH_CHECK("rf_attention");
     return 0;
 }
 
-template <typename T, int D>
-static int launch_attn(const AttnParams& p, int B, hipStream_t st) {
+// The ONE place that decides which kernel an attention call runs (rf_attention launches what it says, rf_attention_plan reports it).
+static int attn_decide(int dtype, int B, int heads, int d, int Nq, int Nk, AttnPlan& pl) {
+    if (!(d == 8 || d == 16 || d == 32 || d == 40 || d == 64 || d == 80 || d == 160)) {
+        set_error("rf_attention: head dim %d not instantiated (have 8,16,32,40,64,80,160)", d);
+        return 1;
+    }
+    const bool h16 = dtype == RF_BF16 || dtype == RF_F16;
+    pl.family = dtype == RF_BF16X3 ? ATTN_X3 : ATTN_GENERIC;
+    pl.storage = dtype == RF_BF16X3 ? RF_F32 : dtype;
+    pl.D = d;
+    pl.QB = 1; pl.keys = 64; pl.waves = 4;
+    const long long bh = (long long)B * heads;
+    const long long blocks256 = (long long)((Nq + 255) / 256) * bh;
     // QB = 2 (two query blocks per wave, every K / V^T fragment feeds two MFMAs) pays for the small head dim when the
     // grid still fills the chip: d=40, N=4096: 687 us vs 739 us; it loses at d=80 (N=1024: 99 us vs 85 us).
-    if constexpr (sizeof(T) == 2 && D <= 40) {
-        if ((long long)((p.Nq + 255) / 256) * B * p.heads >= 512) {
-            // long sequences of whole 64-key tiles: the in-wave software-pipelined kernel
-            if constexpr (D == 40) {
-                if (p.Nk % 128 == 0 && p.Nk >= 1024) return launch_attn_dma<T, D, 128>(p, B, st);
-                if (p.Nk % 64 == 0 && p.Nk >= 1024) return launch_attn_dma<T, D, 64>(p, B, st);
-            }
+    if (h16 && d <= 40 && blocks256 >= 512) {
+        pl.QB = 2;
+        // long sequences of whole 64-key tiles: the in-wave software-pipelined kernel
+        if (d == 40 && Nk >= 1024 && Nk % 64 == 0) {
+            pl.family = ATTN_DMA;
+            pl.keys = Nk % 128 == 0 ? 128 : 64;
+        } else if (Nk >= 1024) {
             // (4-wave blocks: 8-wave blocks -- both waves of a SIMD on one staged tile -- measured 608 vs 586 us at N = 4096)
-            if (p.Nk >= 1024) return launch_attn_qb<T, D, 2, 128>(p, B, st);
-            return launch_attn_qb<T, D, 2>(p, B, st);
+            pl.keys = 128;
+        }
+    } else if (h16 && d == 80) {
+        // d = 80 (the 32x32 / 48x48 levels): 128 keys per stage and 8 waves per block -- both waves of a SIMD share one staged K / V tile, half the barriers;
+        // 73 us against 85 at N = 1024 (tools/archive/run_r04x.sh: 64-key stages with 8 waves 85, 128-key stages with 4 waves 105, two query blocks per wave 81-99).
+        // d = 160 keeps the 4-wave / 64-key form (N = 256: four stages of 64 keys already cover the sequence).
+        if (Nk % 128 == 0 && Nk >= 384) {
+            // whole 128-key tiles: the in-wave software-pipelined kernel, one wave per SIMD
+            pl.family = ATTN_DMA;
+            pl.QB = 2; pl.keys = 128;
+        } else if (Nk >= 512 && blocks256 >= 256) {
+            pl.keys = 128; pl.waves = 8;
         }
     }
-    // d = 80 (the 32x32 / 48x48 levels): 128 keys per stage and 8 waves per block -- both waves of a SIMD share one staged K / V tile, half the barriers;
-    // 73 us against 85 at N = 1024 (tools/archive/run_r04x.sh: 64-key stages with 8 waves 85, 128-key stages with 4 waves 105, two query blocks per wave 81-99).
-    // d = 160 keeps the 4-wave / 64-key form (N = 256: four stages of 64 keys already cover the sequence).
-    if constexpr (sizeof(T) == 2 && D == 80) {
-        // whole 128-key tiles: the in-wave software-pipelined kernel, one wave per SIMD
-        if (p.Nk % 128 == 0 && p.Nk >= 384) return launch_attn_dma<T, D, 128>(p, B, st);
-        if (p.Nk >= 512 && (long long)((p.Nq + 255) / 256) * B * p.heads >= 256) return launch_attn_qb<T, D, 1, 128, 8>(p, B, st);
+    if (pl.family == ATTN_DMA) {
+        pl.stages = attn_dma_ring(pl.keys);
+        pl.lds = attn_dma_lds(d, pl.keys);
+        pl.ones = 1;
+    } else {
+        const int tb = pl.family == ATTN_X3 ? attn_x3_tile_bytes(d, pl.keys) : attn_tile_bytes(h16 ? 2 : 4, d, pl.keys);
+        pl.stages = attn_stages(tb);
+        pl.lds = pl.stages * tb;
+        pl.ones = d % 32 != 0;
     }
-    return launch_attn_qb<T, D, 1>(p, B, st);
+    pl.qpb = 32 * pl.waves * pl.QB;
+    pl.grid = (int)(((Nq + pl.qpb - 1) / pl.qpb) * bh);
+    return 0;
+}
+
+// plan -> instantiation (no decision here: every branch reads the plan)
+template <typename T, int D>
+static int launch_attn(const AttnPlan& pl, const AttnParams& p, int B, hipStream_t st) {
+    if constexpr (sizeof(T) == 2 && D == 40) {
+        if (pl.family == ATTN_DMA) return pl.keys == 128 ? launch_attn_dma<T, D, 128>(pl, p, B, st) : launch_attn_dma<T, D, 64>(pl, p, B, st);
+    }
+    if constexpr (sizeof(T) == 2 && D == 80) {
+        if (pl.family == ATTN_DMA) return launch_attn_dma<T, D, 128>(pl, p, B, st);
+        if (pl.waves == 8) return launch_attn_qb<T, D, 1, 128, 8>(pl, p, B, st);
+    }
+    if constexpr (sizeof(T) == 2 && D <= 40) {
+        if (pl.QB == 2) return pl.keys == 128 ? launch_attn_qb<T, D, 2, 128>(pl, p, B, st) : launch_attn_qb<T, D, 2>(pl, p, B, st);
+    }
+    return launch_attn_qb<T, D, 1>(pl, p, B, st);
 }
 
 template <typename T>
-static int dispatch_attn(const AttnParams& p, int B, hipStream_t st) {
-    switch (p.d) {
-        case 40: return launch_attn<T, 40>(p, B, st);
-        case 64: return launch_attn<T, 64>(p, B, st);
-        case 80: return launch_attn<T, 80>(p, B, st);
-        case 160: return launch_attn<T, 160>(p, B, st);
-        case 8: return launch_attn<T, 8>(p, B, st);
-        case 16: return launch_attn<T, 16>(p, B, st);
-        case 32: return launch_attn<T, 32>(p, B, st);
+static int dispatch_attn(const AttnPlan& pl, const AttnParams& p, int B, hipStream_t st) {
+    switch (pl.D) {
+        case 40: return launch_attn<T, 40>(pl, p, B, st);
+        case 64: return launch_attn<T, 64>(pl, p, B, st);
+        case 80: return launch_attn<T, 80>(pl, p, B, st);
+        case 160: return launch_attn<T, 160>(pl, p, B, st);
+        case 8: return launch_attn<T, 8>(pl, p, B, st);
+        case 16: return launch_attn<T, 16>(pl, p, B, st);
+        case 32: return launch_attn<T, 32>(pl, p, B, st);
         default: break;
     }
-    set_error("rf_attention: head dim %d not instantiated (have 8,16,32,40,64,80,160)", p.d);
+    set_error("rf_attention: head dim %d not instantiated (have 8,16,32,40,64,80,160)", pl.D);
     return 1;
 }
 
@@ -1123,8 +1186,26 @@ extern "C" int rf_attention(int dtype, const void* q, const void* k, const void*
     p.sq = sq; p.sk = sk; p.sv = sv; p.so = so;
     p.scale_log2e = scale * 1.4426950408889634f;
     if (fabsf(p.scale_log2e - 1.0f) < 1e-6f) p.scale_log2e = 1.0f;       // scale = ln 2: the caller's scores are already in the exp2 domain
-    if (dtype == RF_BF16X3) return dispatch_attn_x3(p, B, (hipStream_t)stream);          // fp32 in memory, split-bf16 operand pairs on the bf16 MFMA
-    if (dtype == RF_F32) return dispatch_attn<float>(p, B, (hipStream_t)stream);
-    if (dtype == RF_F16) return dispatch_attn<f16_t>(p, B, (hipStream_t)stream);
-    return dispatch_attn<bf16_t>(p, B, (hipStream_t)stream);
+    AttnPlan pl;
+    if (attn_decide(dtype, B, heads, d, Nq, Nk, pl)) return 1;
+    if (dtype == RF_BF16X3) return dispatch_attn_x3(pl, p, B, (hipStream_t)stream);          // fp32 in memory, split-bf16 operand pairs on the bf16 MFMA
+    if (dtype == RF_F32) return dispatch_attn<float>(pl, p, B, (hipStream_t)stream);
+    if (dtype == RF_F16) return dispatch_attn<f16_t>(pl, p, B, (hipStream_t)stream);
+    return dispatch_attn<bf16_t>(pl, p, B, (hipStream_t)stream);
+}
+
+// The launch plan of an rf_attention call as a host-only query: no pointers, no launch, no device.  info12 = { family (0 generic, 1 x3, 2 dma),
+// storage dtype, D, QB (32-query blocks per wave), keys per stage, waves per block, LDS stages (the ring depth for dma), denominator in the
+// MFMA (0 | 1), queries per block, grid blocks, dynamic LDS bytes, grid % 8 }.
+extern "C" int rf_attention_plan(int dtype, int B, int heads, int d, int Nq, int Nk, int32_t* info12) {
+    using namespace rf;
+    RF_CHECK(dtype == RF_F32 || dtype == RF_BF16 || dtype == RF_F16 || dtype == RF_BF16X3, "rf_attention: bad dtype %d", dtype);
+    RF_CHECK(info12 && B > 0 && heads > 0 && Nq > 0 && Nk > 0, "rf_attention: bad arguments");
+    RF_CHECK(d % 8 == 0, "rf_attention: d/ld alignment (d=%d)", d);
+    RF_CHECK((long long)B * heads * ((Nq + 127) / 128) < (1LL << 31), "rf_attention: grid too large");
+    AttnPlan pl;
+    if (attn_decide(dtype, B, heads, d, Nq, Nk, pl)) return 1;
+    const int32_t w[12] = {pl.family, pl.storage, pl.D, pl.QB, pl.keys, pl.waves, pl.stages, pl.ones, pl.qpb, pl.grid, pl.lds, pl.grid % 8};
+    for (int i = 0; i < 12; ++i) info12[i] = w[i];
+    return 0;
 }

@@ -854,13 +854,43 @@ def attention(q, k, v, out, *, heads, scale, x3=False, name="attention"):
     attention of the "f32x3" parity mode, 2^-16 relative error per product instead of the exact-fp32 MFMA's 2^-24 at a fifth of its time."""
     lib = _lib.load()
     _require_gpu(q, k, v, out)
-    B, Nq, Cc = q.shape
-    Nk = k.shape[1]
-    d = Cc // heads
-    assert q.dtype == k.dtype == v.dtype == out.dtype and (not x3 or q.dtype == torch.float32)
+    B, heads, d, Nq, Nk = _attention_sizes(q, k, v, out, heads, x3)
     return Launch(lib.rf_attention, (RF_BF16X3 if x3 else code(q.dtype), _p(q), _p(k), _p(v), _p(out), B, heads, d, Nq, Nk, q.stride(1), k.stride(1),
                                      v.stride(1), out.stride(1), q.stride(0), k.stride(0), v.stride(0), out.stride(0), float(scale)),
                   (q, k, v, out), name)
+
+
+def _attention_sizes(q, k, v, out, heads, x3):
+    assert q.dim() == k.dim() == v.dim() == out.dim() == 3, "attention: [B, N, heads*d] views"
+    assert q.stride(-1) == 1 and k.stride(-1) == 1 and v.stride(-1) == 1 and out.stride(-1) == 1
+    assert k.shape == v.shape and q.shape[0] == k.shape[0] == out.shape[0] and out.shape == q.shape and q.shape[2] == k.shape[2]
+    assert q.dtype == k.dtype == v.dtype == out.dtype and (not x3 or q.dtype == torch.float32)
+    B, Nq, Cc = q.shape
+    assert heads > 0 and Cc % heads == 0
+    return B, heads, Cc // heads, Nq, k.shape[1]
+
+
+ATTN_FAMILIES = ("generic", "x3", "dma")
+ATTN_PLAN_KEYS = ("family", "storage", "d", "qb", "keys", "waves", "stages", "ones", "qpb", "grid", "lds", "grid_mod8")
+
+
+def attention_plan_of(dtype, B, heads, d, Nq, Nk, x3=False):
+    """The launch plan rf_attention takes for these sizes (rf_attention_plan: host only, no tensors, no launch, no GPU): dict(family = one of
+    ATTN_FAMILIES, storage = dtype code of the tensors, d, qb = 32-query blocks per wave, keys per LDS stage, waves per block, stages (1 | 2, the ring
+    depth 3 | 7 for dma), ones = the softmax denominator rides in the MFMA, qpb = queries per block, grid, lds = dynamic LDS bytes, grid_mod8).
+    Raises RefaceHipError for a head dim that is not instantiated."""
+    lib = _lib.load()
+    info = (C.c_int32 * 12)()
+    _lib.check(lib.rf_attention_plan(RF_BF16X3 if x3 else code(dtype), B, heads, d, Nq, Nk, info), "attention.plan")
+    pl = dict(zip(ATTN_PLAN_KEYS, (int(x) for x in info)))
+    pl["family"] = ATTN_FAMILIES[pl["family"]]
+    return pl
+
+
+def attention_plan(q, k, v, out, *, heads, x3=False):
+    """attention_plan_of for the tensors of an attention() call (device or host tensors: nothing is launched)."""
+    B, heads, d, Nq, Nk = _attention_sizes(q, k, v, out, heads, x3)
+    return attention_plan_of(q.dtype, B, heads, d, Nq, Nk, x3)
 
 
 def softmax_rows(x, name="softmax_rows"):

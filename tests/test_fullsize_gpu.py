@@ -462,6 +462,13 @@ def test_attention_bench_shapes(dt, BH, d, N):
     qkv = qkv.to(dt)
     qkv_d = qkv.to(DEV)
     out = torch.empty((B, N, C_), dtype=dt, device=DEV)
+    # the kernel each benchmark shape runs today: the in-wave pipelined DMA kernel (128-key stages, ring of 3) for 16-bit d = 40 / d = 80, else the
+    # generic kernel with one query block per wave and 64-key stages (a single LDS stage for fp32 d = 160)
+    pl = ops.attention_plan(qkv_d[..., :C_], qkv_d[..., C_:2 * C_], qkv_d[..., 2 * C_:], out, heads=heads)
+    if dt != torch.float32 and d in (40, 80):
+        assert (pl["family"], pl["qb"], pl["keys"], pl["waves"], pl["stages"], pl["grid"]) == ("dma", 2, 128, 4, 3, BH * (N // 256)), pl
+    else:
+        assert (pl["family"], pl["qb"], pl["keys"], pl["waves"], pl["stages"], pl["grid"]) == ("generic", 1, 64, 4, 1 if (dt == torch.float32 and d == 160) else 2, BH * (N // 128)), pl
     ops.attention(qkv_d[..., :C_], qkv_d[..., C_:2 * C_], qkv_d[..., 2 * C_:], out, heads=heads, scale=d ** -0.5)()
     torch.cuda.synchronize()
     # reference on the GPU in fp32 through PyTorch's plain ops, one head at a time (fp32 scores of N = 9216 are 340 MB per head)

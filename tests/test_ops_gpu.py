@@ -240,6 +240,9 @@ def test_attention(dt, heads, d, N):
     qkv, qkvr = q(rnd((B, N, 3 * Cc), 28), dt)
     out = torch.empty((B, N, Cc), dtype=dt, device=DEV)
     scale = d ** -0.5
+    # every shape here runs the generic kernel: one query block per wave, 64-key stages, 4 waves (single-stage LDS only for fp32 d = 160)
+    pl = ops.attention_plan(qkv[..., :Cc], qkv[..., Cc:2 * Cc], qkv[..., 2 * Cc:], out, heads=heads)
+    assert (pl["family"], pl["qb"], pl["keys"], pl["waves"], pl["stages"], pl["ones"]) == ("generic", 1, 64, 4, 1 if (dt == torch.float32 and d == 160) else 2, int(d % 32 != 0)), pl
     ops.attention(qkv[..., :Cc], qkv[..., Cc:2 * Cc], qkv[..., 2 * Cc:], out, heads=heads, scale=scale)()
     torch.cuda.synchronize()
     sp = lambda t: t.reshape(B, N, heads, d).transpose(1, 2)
@@ -261,6 +264,9 @@ def test_attention_x3_vs_fp64(heads, d, N):
     scale = d ** -0.5 * 2.0
     out = torch.empty((B, N, C_), dtype=torch.float32, device=DEV)
     out32 = torch.empty_like(out)
+    pl, pl32 = ops.attention_plan(qq, kk, vv, out, heads=heads, x3=True), ops.attention_plan(qq, kk, vv, out32, heads=heads)
+    assert (pl["family"], pl["qb"], pl["keys"], pl["waves"], pl["stages"]) == ("x3", 1, 64, 4, 1 if d == 160 else 2), pl
+    assert (pl32["family"], pl32["qb"], pl32["keys"], pl32["waves"], pl32["stages"]) == ("generic", 1, 64, 4, 1 if d == 160 else 2), pl32
     ops.attention(qq, kk, vv, out, heads=heads, scale=scale, x3=True)()
     ops.attention(qq, kk, vv, out32, heads=heads, scale=scale)()
     torch.cuda.synchronize()
@@ -324,6 +330,12 @@ def test_attention_pipelined_kernels(d, Nq, Nk, mode, dt):
     kd, kr = q(kx, dt)
     vd, vr = q(vx, dt)
     out = torch.empty((B, Nq, Cc), dtype=dt, device=DEV)
+    # the conditions of the docstring as the plan the library reports: the DMA kernel, 64-key stages in a ring of 7 for d = 40 with a key count that is
+    # no multiple of 128, else 128-key stages in a ring of 3; d = 40 only with >= 512 blocks of 256 queries
+    pl = ops.attention_plan(qd, kd, vd, out, heads=heads)
+    kt = 64 if (d == 40 and Nk % 128) else 128
+    assert (pl["family"], pl["d"], pl["qb"], pl["keys"], pl["waves"], pl["stages"], pl["ones"], pl["qpb"]) == ("dma", d, 2, kt, 4, 7 if kt == 64 else 3, 1, 256), pl
+    assert pl["grid"] == B * heads * ((Nq + 255) // 256) and (d == 80 or pl["grid"] >= 512), pl
     ops.attention(qd, kd, vd, out, heads=heads, scale=scale)()
     torch.cuda.synchronize()
     ref = _attn_ref(qr, kr, vr, heads, d, scale)
