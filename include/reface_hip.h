@@ -353,6 +353,18 @@ int rf_ddim_pack_input(const float* img, const float* z_inpaint, const float* ma
 int rf_ddim_update(const float* eps, int ld_eps, int cfg, float scale, float* img, float* pred_x0, const float* noise,
                    int B, int hw, const float* coefs, void* stream);
 
+/*
+ * DPM-Solver++ multistep update (data prediction), the few-step alternative to rf_ddim_update on the same layouts:
+ *   e = e_u + s (e_c - e_u) when cfg;  m0 = (x - sigma_i e) / alpha_i;
+ *   x' = A x + k0 m0 + k1 m1 + k2 m2 (in place into img);  then the history shifts: m2 <- m1, m1 <- m0.
+ * `coefs` is a DEVICE array of 8 fp32 {alpha_i, sigma_i, A, k0, k1, k2, n_hist, 0} (reface_amd/dpm_solver.py::dpm_coefficients), so a captured
+ * hipGraph of a step can be replayed for every step.  n_hist = 0, 1 or 2 says how many history terms enter the sum: the others are not read
+ * into it (the buffers of a first step are uninitialised).  m1 doubles as the pred_x0 output.  m2 may be NULL when no row has n_hist = 2
+ * (orders 1 and 2).  img, m1, m2: distinct fp32 NCHW [B, 4, hw] buffers.
+ */
+int rf_dpm_update(const float* eps, int ld_eps, int cfg, float scale, float* img, float* m1, float* m2, int B, int hw,
+                  const float* coefs, void* stream);
+
 /* Layout / dtype helpers. */
 int rf_nchw_to_nhwc(const float* x, int B, int C, int HW, int out_dtype, void* out, int Cpad, void* stream);
 int rf_nhwc_to_nchw(int dtype, const void* x, int B, int C, int HW, int ldx, float* out, void* stream);

@@ -56,6 +56,39 @@ __global__ void ddim_update_kernel(const float* __restrict__ eps, int ld, int cf
     if (pred_x0) pred_x0[i] = px0;
 }
 
+// DPM-Solver++ multistep (data prediction) on the layouts of ddim_update_kernel.  Every order of the solver is linear in the latent and the
+// data predictions of this and the last two steps: x' = A x + k0 m0 + k1 m1 + k2 m2 with m0 = (x - sigma e) / alpha.
+// coefs (device, fp32): {alpha_i, sigma_i, A, k0, k1, k2, n_hist, 0}.  n_hist (0, 1 or 2) history terms enter the sum; the others are not read
+// into it (the buffers of a first step hold whatever was there, and 0 * NaN is NaN).  The history shifts in the same pass: m2 <- m1, m1 <- m0.
+__global__ void dpm_update_kernel(const float* __restrict__ eps, int ld, int cfg, float scale, float* __restrict__ img,
+                                  float* __restrict__ m1, float* __restrict__ m2, int B, int hw, const float* __restrict__ coefs) {
+    const float alpha = coefs[0], sigma = coefs[1], A = coefs[2], k0 = coefs[3], k1 = coefs[4], k2 = coefs[5];
+    const int n_hist = (int)coefs[6];
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // over B*4*hw
+    if (i >= (long long)B * 4 * hw) return;
+    const int p = (int)(i % hw);
+    const int c = (int)((i / hw) % 4);
+    const int b = (int)(i / ((long long)4 * hw));
+    float e;
+    if (cfg) {
+        const float eu = eps[((long long)b * hw + p) * ld + c];
+        const float ec = eps[((long long)(B + b) * hw + p) * ld + c];
+        e = eu + scale * (ec - eu);
+    } else {
+        e = eps[((long long)b * hw + p) * ld + c];
+    }
+    const float x = img[i];
+    const float m0 = (x - sigma * e) / alpha;
+    float xp = A * x + k0 * m0;
+    float h1 = 0.f;
+    if (n_hist >= 1 || m2) h1 = m1[i];              // the shift needs it even when the sum does not
+    if (n_hist >= 1) xp += k1 * h1;
+    if (n_hist >= 2 && m2) xp += k2 * m2[i];
+    img[i] = xp;
+    if (m2) m2[i] = h1;
+    m1[i] = m0;
+}
+
 template <typename TO>
 __global__ void nchw_to_nhwc_kernel(const float* __restrict__ x, int B, int C, int HW, TO* __restrict__ out, int Cpad) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // over B*HW*Cpad (output order)
@@ -247,6 +280,16 @@ extern "C" int rf_ddim_update(const float* eps, int ld_eps, int cfg, float scale
     hipLaunchKernelGGL(ddim_update_kernel, grid1d((long long)B * 4 * hw), dim3(256), 0, (hipStream_t)stream, eps, ld_eps, cfg, scale, img,
                        pred_x0, noise, B, hw, coefs);
     RF_LAUNCH_CHECK("rf_ddim_update");
+    return 0;
+}
+
+extern "C" int rf_dpm_update(const float* eps, int ld_eps, int cfg, float scale, float* img, float* m1, float* m2, int B, int hw,
+                             const float* coefs, void* stream) {
+    RF_CHECK(eps && img && m1 && coefs && B > 0 && hw > 0 && ld_eps >= 4, "rf_dpm_update: bad arguments");
+    RF_CHECK(m1 != img && m2 != img && m2 != m1, "rf_dpm_update: img, m1 and m2 must be distinct buffers");
+    hipLaunchKernelGGL(dpm_update_kernel, grid1d((long long)B * 4 * hw), dim3(256), 0, (hipStream_t)stream, eps, ld_eps, cfg, scale, img,
+                       m1, m2, B, hw, coefs);
+    RF_LAUNCH_CHECK("rf_dpm_update");
     return 0;
 }
 

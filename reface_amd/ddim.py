@@ -94,13 +94,28 @@ class DDIMSampler(object):
         px0 = torch.empty((B, 4, H, W), dtype=F32, device=dev)
         noise = torch.zeros((B, 4, H, W), dtype=F32, device=dev) if with_noise else None
         coef = torch.zeros(8, dtype=F32, device=dev)
+        plan = dict(eng=eng, img=img, z=z, m=m, px0=px0, noise=noise, coef=coef, graphs={}, cfg_on=cfg_on, scale=scale,
+                    x_start=torch.empty_like(img), warm=False)
         step = [ops.ddim_pack_input(img, z, m, eng.x_in, dup=2 if cfg_on else 1)]
         step += eng.main
-        step.append(ops.ddim_update(eng.eps, img, px0, noise, coef, cfg=cfg_on, scale=scale))
-        plan = dict(eng=eng, img=img, z=z, m=m, px0=px0, noise=noise, coef=coef, step=step, graphs={}, cfg_on=cfg_on, scale=scale,
-                    x_start=torch.empty_like(img), warm=False)
+        step.append(self._update_launch(plan, noise, coef))
+        plan["step"] = step
         self._plans = {key: plan}
         return plan
+
+    def _update_launch(self, plan, noise, coef):
+        """The launch that closes a step: guided eps -> img / pred_x0, with the step's noise slab and its 8-float coefficient row (device)."""
+        return ops.ddim_update(plan["eng"].eps, plan["img"], plan["px0"], noise, coef, cfg=plan["cfg_on"], scale=plan["scale"])
+
+    _name = "DDIM"
+    _step_draws = True      # the reference's one torch.randn per step (see ddim_sampling)
+
+    def _step_tables(self):
+        """What the unrolled steps index by position: (timesteps in sampling order [S], host coefficient rows [S, 8] fp32, any sigma != 0)."""
+        S = self.ddim_timesteps.shape[0]
+        coefs = torch.flip(self.ddim_coefs, dims=[0]).contiguous()              # row i <-> index S-1-i
+        coefs = torch.cat([coefs, torch.zeros((S, 3), dtype=F32)], dim=1).contiguous()
+        return np.flip(self.ddim_timesteps), coefs, bool((np.asarray(self.ddim_sigmas, dtype=np.float64) != 0).any())
 
     @staticmethod
     def _chunk(S, flagged, want):
@@ -125,8 +140,7 @@ class DDIMSampler(object):
         hi = lo + eng.emb_table.numel() * 4
         patch = [(l.keep[0], l.keep[0].rowvec) for l in eng.main
                  if l.fn.__name__ == "rf_conv_gemm" and l.keep[0].rowvec and lo <= l.keep[0].rowvec < hi]
-        updates = [ops.ddim_update(eng.eps, plan["img"], plan["px0"], None if g["noise"] is None else g["noise"][j], g["coef"][j],
-                                   cfg=plan["cfg_on"], scale=plan["scale"]) for j in range(c)]
+        updates = [self._update_launch(plan, None if g["noise"] is None else g["noise"][j], g["coef"][j]) for j in range(c)]
         pack = plan["step"][0]
         graph = torch.cuda.CUDAGraph()
         try:
@@ -162,11 +176,8 @@ class DDIMSampler(object):
         else:
             raise Exception("kwargs must contain either 'test_model_kwargs' or 'rest' key")
         cfg_on = not (unconditional_conditioning is None or unconditional_guidance_scale == 1.)
-        timesteps = self.ddim_timesteps
-        S = total_steps = timesteps.shape[0]
-        time_range = np.flip(timesteps)
-        sig_host = np.asarray(self.ddim_sigmas, dtype=np.float64)
-        with_noise = bool((sig_host != 0).any())
+        time_range, coefs, with_noise = self._step_tables()
+        S = total_steps = len(time_range)
 
         plan = self._plan(B, H, W, cfg_on, unconditional_guidance_scale, with_noise)
         eng, img, x_start = plan["eng"], plan["img"], plan["x_start"]
@@ -182,13 +193,12 @@ class DDIMSampler(object):
         t_all = torch.tensor(np.ascontiguousarray(time_range), dtype=F32, device=dev)
         table = torch.empty((S, eng.E), dtype=F32, device=dev)
         ops.run(eng.make_emb_launches(t_all, table))
-        coefs = torch.flip(self.ddim_coefs, dims=[0]).contiguous().to(dev)      # row i <-> index S-1-i
-        coefs = torch.cat([coefs, torch.zeros((S, 3), dtype=F32, device=dev)], dim=1).contiguous()
+        coefs = coefs.to(dev)
         # The reference draws torch.randn(shape) on the device at EVERY step, used or not (ddim.py:371 via util.py:264-267: at eta = 0 the
         # draw is multiplied by sigma = 0).  The same S separate draws are made here, up front and in the same order behind the x_T draw, so
         # that the device generator leaves a sample() call in the reference's state (seeded runs stay aligned from batch to batch) and, at
         # eta > 0, the steps see the reference's numbers.
-        if x_noise is None:
+        if x_noise is None and self._step_draws:
             draws = [torch.randn(shape, device=dev) for _ in range(S)]
         if with_noise:
             noise_all = x_noise.to(device=dev, dtype=F32) if x_noise is not None else torch.stack(draws)
@@ -221,7 +231,7 @@ class DDIMSampler(object):
 
         intermediates = {"x_inter": [img.clone()], "pred_x0": [img.clone()]}
         if verbose:
-            print(f"Running DDIM Sampling with {total_steps} timesteps")
+            print(f"Running {self._name} Sampling with {total_steps} timesteps")
         if g is not None:
             for r in range(S // c_steps):
                 i0, i1 = r * c_steps, (r + 1) * c_steps

@@ -918,6 +918,17 @@ def ddim_update(eps, img, pred_x0, noise, coefs, *, cfg, scale, name="ddim_updat
                                        _p(coefs)), (eps, img, pred_x0, noise, coefs), name)
 
 
+def dpm_update(eps, img, m1, m2, coefs, *, cfg, scale, name="dpm_update"):
+    """coefs: device fp32 [8] = {alpha_i, sigma_i, A, k0, k1, k2, n_hist, 0} (dpm_solver.dpm_coefficients); m2 may be None for orders 1 and 2."""
+    lib = _lib.load()
+    _require_gpu(eps, img, m1, m2, coefs)
+    B, _, h, w = img.shape
+    assert eps.dtype == torch.float32 and coefs.dtype == torch.float32 and coefs.numel() >= 8
+    assert all(t is None or (t.dtype == torch.float32 and t.shape == img.shape and t.is_contiguous()) for t in (img, m1, m2))
+    return Launch(lib.rf_dpm_update, (_p(eps), eps.shape[-1], int(cfg), float(scale), _p(img), _p(m1), _p(m2), B, h * w, _p(coefs)),
+                  (eps, img, m1, m2, coefs), name)
+
+
 def nchw_to_nhwc(x, out, name="nchw_to_nhwc"):
     lib = _lib.load()
     _require_gpu(x, out)

@@ -40,7 +40,10 @@ def build_parser():
     p.add_argument("--skip_grid", action="store_true")
     p.add_argument("--skip_save", action="store_true", help="do not save individual samples. For speed measurements.")
     p.add_argument("--ddim_steps", type=int, default=50)
-    p.add_argument("--plms", action="store_true")
+    step_rule = p.add_mutually_exclusive_group()          # one step rule per run: DDIM (default), --plms or --dpm_solver
+    step_rule.add_argument("--plms", action="store_true")
+    step_rule.add_argument("--dpm_solver", action="store_true", help="DPM-Solver++ multistep sampler (not in the reference): made for few steps, "
+                           "e.g. --ddim_steps 20; --ddim_eta must be 0")
     p.add_argument("--laion400m", action="store_true")
     p.add_argument("--fixed_code", action="store_true")
     p.add_argument("--Guidance", action="store_true")
@@ -64,6 +67,9 @@ def build_parser():
     p.add_argument("--rank", type=int, default=0)
     p.add_argument("--precision", type=str, choices=["full", "fullx3", "autocast", "bf16", "fp16", "fp8", "fp8c"], default="full")
     # additions (not in the reference)
+    p.add_argument("--dpm_order", type=int, choices=[1, 2, 3], default=2, help="--dpm_solver: order of the multistep rule")
+    p.add_argument("--dpm_spacing", type=str, choices=["logsnr", "quad", "uniform"], default="logsnr", help="--dpm_solver: the timestep grid "
+                   "(uniform in log-SNR, quadratic in t, or DDIM's own)")
     p.add_argument("--n_items", type=int, default=8, help="number of synthetic pairs (--dataset synthetic)")
     p.add_argument("--dump_tensors", type=str, default=None, help="directory for per-batch .npz dumps of the tensors fed to / produced by the engines (tests)")
     p.add_argument("--clip_vision_config", type=str, default=None, help="JSON dict overriding the CLIP ViT dims (tests)")
@@ -140,6 +146,9 @@ def main(argv=None):
     if opt.plms:                                    # inference_test_bench.py:337-339
         from ldm.models.diffusion.plms import PLMSSampler
         sampler = PLMSSampler(model)
+    elif opt.dpm_solver:
+        from ldm.models.diffusion.dpm_solver import DPMSolverSampler
+        sampler = DPMSolverSampler(model, order=opt.dpm_order, spacing=opt.dpm_spacing)
     else:
         sampler = DDIMSampler(model)
 
