@@ -616,6 +616,35 @@ int rf_lpips_total(const double* vals, int B, int L, double* d, double* totals, 
 /* elementwise y = silu(x) on fp32 (emb path, openaimodel.py:219) */
 int rf_silu_f32(const float* x, float* y, int64_t n, void* stream);
 
+/*
+ * PNG encoding of device-resident images (the CLIs' --gpu_png; reface_amd/pngenc.py wraps the result in the PNG signature and chunks).
+ * The filtered stream of an image is cut into segments of RF_PNG_SEG bytes; a segment is coded without reference to any other and its bytes
+ * land in a slot of RF_PNG_SLOT bytes (the stored worst case, segment + 5, rounded up to 16).  n is a stream's length in bytes and
+ * nseg = ceil(n / RF_PNG_SEG); all streams of a call share n.
+ *   rf_png_filter_u8        : images u8 [B, H, W, C], C = 1 | 3 | 4 (image b at images + b * image_stride, row y at + y * row_stride bytes)
+ *                             -> out (stream b at out + b * out_stride): H rows of 1 + W * C bytes, the filter type then the filtered row.
+ *                             None / Sub / Up / Average / Paeth in exact integer arithmetic; per row the filter with the smallest sum of
+ *                             |residual as a signed byte| wins, ties to the lowest type.
+ *   rf_png_deflate_segments : streams u8 (stream b at streams + b * stream_stride; any alignment) -> slots u8 [B, nseg, RF_PNG_SLOT] (16-byte
+ *                             aligned), seg_bytes int32 [B, nseg] (the bytes written to each slot) and seg_adler uint32 [B, nseg] (the
+ *                             segment's Adler-32 partial: sum of bytes | (sum of (len - i) * byte_i) << 16, each mod 65521).  Tokens as in
+ *                             zlib's Z_RLE strategy (distance 1 only); one dynamic block per segment with a fixed-form header (HLIT = 29,
+ *                             HDIST = 0, a complete 4-bit code-length code over 0..15); Huffman lengths by the two-queue construction over
+ *                             leaves sorted by (count, symbol), the leaf taken on equal weight, counts halved (rounding up) while a code is
+ *                             deeper than 15.  Every segment but the last ends with an empty stored block (byte aligned); the last one's block
+ *                             carries BFINAL.  A segment that is not smaller than segment + 5 bytes this way is one stored block.
+ *   rf_png_pack             : -> out u8 (stream b at out + b * out_stride, out_stride >= n + 5 * nseg + 6): the zlib header 78 01, the
+ *                             segments back to back, the combined Adler-32; lengths int32 [B] = the stream's bytes.
+ */
+#define RF_PNG_SEG 32768
+#define RF_PNG_SLOT 32784
+int rf_png_filter_u8(const void* images_u8, int B, int H, int W, int C, int64_t image_stride, int64_t row_stride, void* out_u8, int64_t out_stride,
+                     void* stream);
+int rf_png_deflate_segments(const void* streams_u8, int B, int64_t n, int64_t stream_stride, void* slots_u8, int* seg_bytes, uint32_t* seg_adler,
+                            void* stream);
+int rf_png_pack(const void* slots_u8, const int* seg_bytes, const uint32_t* seg_adler, int B, int64_t n, void* out_u8, int64_t out_stride,
+                int* lengths, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

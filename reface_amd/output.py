@@ -133,7 +133,7 @@ ENCODE_ORDER = ("result", "grid", "GT", "inpaint", "ref", "mask")
 class OutputWriter:
     """PNG encoding off the launch thread: ``submit`` takes host arrays of one batch and returns at once; ``close`` drains."""
 
-    def __init__(self, outdir, skip_grid=False, depth=4, threads=8, compress_level=None, aux_compress_level=None):
+    def __init__(self, outdir, skip_grid=False, depth=4, threads=8, compress_level=None, aux_compress_level=None, png_encoder=None):
         # One job per FILE, `threads` workers: the six PNG encodes of an image are ~0.3 s of zlib on incompressible content (zlib runs
         # outside the GIL), so a single worker caps the CLI at ~3 images/s -- below one MI355X (tools/host_scaling_probe.py: 2.86 s per
         # batch of 8 with one worker against 0.9 s of device time)
@@ -144,6 +144,9 @@ class OutputWriter:
         # compares with the reference's -- keeps `compress_level`
         self.save_kw = {} if compress_level is None else {"compress_level": int(compress_level)}
         self.aux_kw = self.save_kw if aux_compress_level is None else {"compress_level": int(aux_compress_level)}
+        # png_encoder (--gpu_png): a reface_amd.pngenc.PngEncoder; ``encode_device`` / ``submit_device`` then encode the records on the GPU and
+        # the workers only copy the compressed bytes and write them.  The host path above is untouched.
+        self.png_encoder = png_encoder
         self.q = queue.Queue(maxsize=depth * 8 * len(ENCODE_ORDER))
         self.err = None
         self.n = 0                 # images whose files are all on disk
@@ -160,6 +163,9 @@ class OutputWriter:
             if job is None:
                 return
             try:
+                if len(job) == 3:          # a device encode of one file kind for a whole batch (--gpu_png): wait, copy the streams, write
+                    self._write_device(*job)
+                    continue
                 if len(job) == 6:          # float panels of one image (the host-composed path): compose here, off the launch thread, then
                     sid = job[0]           # hand the files to whoever is free -- or encode them here when the queue is full (never block a worker)
                     arrs = compose(*job[1:], skip_grid=self.skip_grid)
@@ -185,6 +191,40 @@ class OutputWriter:
             if self.left[sid] == 0:
                 del self.left[sid]
                 self.n += 1
+
+    def _write_device(self, ids, key, png_job):
+        for sid, data in zip(ids, png_job.result()):
+            with open(paths(self.outdir, sid)[key], "wb") as f:
+                f.write(data)
+            with self.lock:
+                self.left[sid] -= 1
+                if self.left[sid] == 0:
+                    del self.left[sid]
+                    self.n += 1
+
+    def encode_device(self, records, H, W):
+        """Launch thread, right behind rf_compose_outputs_u8: enqueue the PNG encodes of a batch's packed records (uint8 DEVICE tensor
+        [B, record_bytes]) on the current stream -> [(file kind, PngJob)].  Nothing waits; hand the list to ``submit_device`` once the next
+        batch has been enqueued."""
+        if self.png_encoder is None:
+            raise RuntimeError("OutputWriter.encode_device needs a png_encoder")
+        _, lay = record_layout(H, W, with_grid=not self.skip_grid)
+        jobs = []
+        for key in ENCODE_ORDER:
+            if key in lay:
+                o, shp = lay[key]
+                jobs.append((key, self.png_encoder.encode_async(records[:, o:o + int(np.prod(shp))].unflatten(1, shp))))
+        return jobs
+
+    def submit_device(self, ids, jobs):
+        if self.err is not None:
+            raise self.err
+        ids = list(ids)
+        with self.lock:
+            for sid in ids:
+                self.left[sid] = self.left.get(sid, 0) + len(jobs)
+        for key, job in jobs:
+            self.q.put((ids, key, job))
 
     def _enqueue(self, per_image):
         """per_image: [(sid, {name: uint8 HWC array})] of one batch -> one job per file, long encodes first."""

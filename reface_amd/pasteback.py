@@ -165,9 +165,11 @@ class PngWriter:
     """PNG encodes of whole pasted frames off the launch thread (one job per file, like output.OutputWriter).  At most `depth` frames wait
     (``submit`` then blocks on the oldest: a 1080p RGBA frame is 8 MB of host memory); ``close`` drains and raises the first error."""
 
-    def __init__(self, threads=None, depth=32):
+    def __init__(self, threads=None, depth=32, png_encoder=None):
         self.pool = ThreadPoolExecutor(max_workers=threads or max(2, min(8, available_cpus() // 2)))
         self.pending, self.depth, self.n = [], int(depth), 0
+        # png_encoder (--gpu_png): a reface_amd.pngenc.PngEncoder for ``encode_device`` / ``submit_device``; ``submit`` stays the host path
+        self.png_encoder = png_encoder
 
     @staticmethod
     def _save(path, arr):
@@ -182,6 +184,29 @@ class PngWriter:
     def submit(self, path, arr):
         self._reap(block=True)
         self.pending.append(self.pool.submit(self._save, path, arr))
+
+    @staticmethod
+    def _write(paths, png_job):
+        for path, data in zip(paths, png_job.result()):
+            with open(path, "wb") as f:
+                f.write(data)
+
+    def encode_device(self, frames):
+        """Launch thread: enqueue the PNG encodes of uint8 DEVICE frames [H, W, 3 | 4] on the current stream, frames of one shape as ONE
+        batched encode (3 launches per shape, not per frame) -> [(indices into `frames`, PngJob)].  Nothing waits."""
+        if self.png_encoder is None:
+            raise RuntimeError("PngWriter.encode_device needs a png_encoder")
+        groups = {}
+        for i, f in enumerate(frames):
+            groups.setdefault(tuple(f.shape), []).append(i)
+        return [(idx, self.png_encoder.encode_async(torch.stack([frames[i] for i in idx]))) for idx in groups.values()]
+
+    def submit_device(self, paths, png_job):
+        """Hand an enqueued encode to the pool: a worker waits for its event, copies the compressed bytes and writes the files `paths` (one per
+        image of the job, in order)."""
+        self._reap(block=True)
+        self.pending.append(self.pool.submit(self._write, list(paths), png_job))
+        self.n += len(paths) - 1          # (a reaped job counts once; its other files are counted here)
 
     def close(self):
         try:

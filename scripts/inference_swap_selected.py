@@ -80,6 +80,8 @@ def build_parser():
     p.add_argument("--dump_tensors", type=str, default=None, help="directory for per-batch .npz dumps of the tensors fed to / produced by the engines (tests)")
     p.add_argument("--clip_vision_config", type=str, default=None, help="JSON dict overriding the CLIP ViT dims (tests)")
     p.add_argument("--num_workers", type=int, default=4)
+    p.add_argument("--gpu_png", action="store_true", help="compose and encode the six PNG files per image on the GPU (reface_amd/pngenc.py): the same "
+                   "pixels, other file bytes (about zlib level 1 in size)")
     p.add_argument("--parse_masks", action="store_true", help="write missing face-parsing label maps from the existing crops with the GPU "
                    "face parser (--faceParsing_ckpt, 'none' = seeded weights; --seg12) before sampling")
     p.add_argument("--align", action="store_true", help="stage 1: align the images of --target_folder / --src_folder on the GPU from their 68 "
@@ -112,6 +114,25 @@ def check_align_inputs(opt):
     if problems:
         raise SystemExit("inference_swap_selected: --align needs the image folders and 68 landmarks per image; problems:\n  " + "\n  ".join(problems))
     return jobs
+
+
+def save_gpu_png(enc, device, x_img, target, kw, ref512, ids, dirs):
+    """--gpu_png: a batch's six files per image from the packed device records.  The encodes of all six kinds are enqueued before the first is
+    fetched, but they are fetched here, on the launch thread, before the next batch starts: like this caller's host path, and unlike the
+    test-bench and video callers, it does not overlap saving with sampling."""
+    from reface_amd import ops
+    B, _, H, W = x_img.shape
+    nbytes, lay = O.record_layout(H, W, with_grid=True)
+    rec = torch.zeros((B, nbytes), dtype=torch.uint8, device=device)          # (zeros: the grid's padding is never written)
+    dev = lambda t: t.to(device, non_blocking=True).float().contiguous()
+    ops.compose_outputs_u8(x_img.contiguous(), dev(target), dev(kw["inpaint_image"]), dev(kw["inpaint_mask"]), ref512.contiguous(), rec, with_grid=True)()
+    jobs = {k: enc.encode_async(rec[:, o:o + int(np.prod(shp))].unflatten(1, shp)) for k, (o, shp) in lay.items()}
+    for k, job in jobs.items():
+        for sid, data in zip(ids, job.result()):
+            path = (os.path.join(dirs["results"], sid + ".png") if k == "result" else os.path.join(dirs["grid"], "grid-" + sid + ".png") if k == "grid"
+                    else os.path.join(dirs["samples"], f"{sid}_{k}.png"))
+            with open(path, "wb") as f:
+                f.write(data)
 
 
 def main(argv=None):
@@ -165,6 +186,10 @@ def main(argv=None):
     from reface_amd.data import VideoDataset, load_source_reference
     from reface_amd.pipeline import SwapRunner
     runner = SwapRunner(model, sampler, opt)
+    png_encoder = None
+    if opt.gpu_png and not opt.skip_save:
+        from reface_amd.pngenc import PngEncoder
+        png_encoder = PngEncoder(device)
     outpath = opt.outdir
     model_out = os.path.join(outpath, "model_outputs")
     os.makedirs(model_out, exist_ok=True)
@@ -196,6 +221,9 @@ def main(argv=None):
                     Image.fromarray(O.to_u8_hwc(img0)).save(os.path.join(model_out, f"_intermediate_{k}.png"))
                 n_done += B
                 if opt.skip_save:
+                    continue
+                if opt.gpu_png:          # panels + grid composed by rf_compose_outputs_u8 (the bytes of O.compose), encoded on the device
+                    save_gpu_png(png_encoder, device, x_img, test_batch, kw, runner.resized_reference(ref, opt.H, opt.W), list(ids), dirs)
                     continue
                 ref_np = runner.resized_reference(ref, opt.H, opt.W).cpu().numpy()
                 res, tgt, inp, msk = x_img.cpu().numpy(), test_batch.float().numpy(), kw["inpaint_image"].cpu().numpy(), kw["inpaint_mask"].float().cpu().numpy()

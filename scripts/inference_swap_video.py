@@ -121,6 +121,9 @@ def build_parser():
     p.add_argument("--stream", action="store_true", help="raw frames to pasted frames as one device-resident chain: the work of --align --parse_masks "
                    "--paste_back with one PNG decode and one encode per frame and no intermediate files (reads what they read; writes results/, "
                    "<video>_inv_transforms.npy and temp_results/)")
+    p.add_argument("--gpu_png", action="store_true", help="--paste_back / --stream: encode the pasted RGBA frames of results/ on the GPU "
+                   "(reface_amd/pngenc.py): the same pixels, other file bytes (about zlib level 1 in size); crops, label maps and model_outputs "
+                   "stay on the host writer")
     p.add_argument("--stream_keep", action="store_true", help="--stream: also write <video>cropped_face/, <video>mask_frames/ and model_outputs/ "
                    "of the swapped frames, from the device bytes, off the launch thread")
     return p
@@ -263,8 +266,9 @@ def run_stream(opt):
     start_code = None
     if opt.fixed_code:
         start_code = torch.randn([opt.C, opt.H // opt.f, opt.W // opt.f], device=device).unsqueeze(0).repeat(opt.n_samples, 1, 1, 1)
-    writer = None if opt.skip_save else PngWriter()
+    writer = None if opt.skip_save else PngWriter(png_encoder=make_png_encoder(opt, device))
     n_done = 0
+    held = []          # --gpu_png: the previous batch's enqueued encodes, handed to the writer only after this batch has been enqueued
     with torch.no_grad(), model.ema_scope():
         for frames, ids in loader:          # (the iterator draws its base seed from the CPU generator, as the staged loader's does)
             test_batch, kw, state = vs.prepare(frames, ids)
@@ -276,13 +280,18 @@ def run_stream(opt):
             n_done += B
             if writer is None:
                 continue
-            for sid, frame in zip(ids, pasted):
-                writer.submit(os.path.join(results, sid + ".png"), frame.cpu().numpy())
+            if opt.gpu_png:
+                held = hand_over(writer, held, [([os.path.join(results, ids[i] + ".png") for i in idx], job) for idx, job in writer.encode_device(pasted)])
+            else:
+                for sid, frame in zip(ids, pasted):
+                    writer.submit(os.path.join(results, sid + ".png"), frame.cpu().numpy())
             if keep:
                 for sid, i, crop, lab, mo in zip(ids, state["index"], state["crops"].cpu().numpy(), state["labels"].cpu().numpy(), swapped.cpu().numpy()):
                     writer.submit(os.path.join(keep["crops"], f"{i}.png"), crop)
                     writer.submit(os.path.join(keep["masks"], f"{i}.png"), lab)
                     writer.submit(os.path.join(keep["model_outputs"], sid + ".png"), mo)
+    if writer is not None:
+        hand_over(writer, held, [])
     torch.cuda.synchronize()
     n_files = writer.close() if writer is not None else 0
     n_pasted = n_files // 4 if keep else n_files
@@ -296,9 +305,29 @@ def run_stream(opt):
     return n_done
 
 
+def make_png_encoder(opt, device):
+    """--gpu_png: the device PNG encoder the pasted frames go through (None: the host writer)."""
+    if not opt.gpu_png:
+        return None
+    from reface_amd.pngenc import PngEncoder
+    return PngEncoder(device)
+
+
+def hand_over(writer, held, jobs):
+    """The encodes enqueued one batch ago go to the writer threads now that the next batch is behind them in the stream; returns what to hold."""
+    for paths, job in held:
+        writer.submit_device(paths, job)
+    return jobs
+
+
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     print(opt)
+    if opt.gpu_png and not (opt.paste_back or opt.stream or opt.stream_keep):
+        raise SystemExit("inference_swap_video: --gpu_png encodes the pasted frames of results/ and needs --paste_back or --stream "
+                         "(model_outputs/ stays on the host writer)")
+    if opt.gpu_png and opt.skip_save:
+        print("inference_swap_video: --skip_save writes no files, so --gpu_png has nothing to encode")
     if opt.stream or opt.stream_keep:
         opt.stream = True
         return run_stream(opt)
@@ -351,7 +380,8 @@ def main(argv=None):
     if opt.paste_back and not opt.skip_save:
         from reface_amd.pasteback import PasteBack, PngWriter
         sp = pasteback_paths(opt)
-        paster, writer = PasteBack(sp["video_frames"], sp["inv_transforms"]), PngWriter()
+        paster, writer = PasteBack(sp["video_frames"], sp["inv_transforms"]), PngWriter(png_encoder=make_png_encoder(opt, device))
+    held = []
     with torch.no_grad(), model.ema_scope():
         for test_batch, prior, kw, ids in loader:
             frames = paster.prefetch(ids) if paster is not None else None          # decoded on the pool while the batch samples
@@ -366,9 +396,16 @@ def main(argv=None):
             res = x_img.cpu().numpy()
             for i, sid in enumerate(ids):
                 Image.fromarray(O.to_u8_hwc(res[i])).resize((1024, 1024), Image.BILINEAR).save(os.path.join(model_out, sid + ".png"))
-            if paster is not None:          # stage 3 (:705-724): the crops enlarged and warped into their frames on the device, PNGs encoded off this thread
+            if paster is not None and opt.gpu_png:          # the pasted frames stay on the device and are encoded there
+                dev_frames = [torch.from_numpy(np.array(f.result(), copy=True)).to(device) for f in frames]
+                pasted = paster.paste_device(x_img, ids, dev_frames)
+                held = hand_over(writer, held, [([os.path.join(opt.outdir, "results", ids[i] + ".png") for i in idx], job)
+                                                for idx, job in writer.encode_device(pasted)])
+            elif paster is not None:          # stage 3 (:705-724): the crops enlarged and warped into their frames on the device, PNGs encoded off this thread
                 for sid, frame in zip(ids, paster.paste(x_img, ids, frames)):
                     writer.submit(os.path.join(opt.outdir, "results", sid + ".png"), frame)
+    if writer is not None:
+        hand_over(writer, held, [])
     torch.cuda.synchronize()
     if paster is not None:
         paster.close()

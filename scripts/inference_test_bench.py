@@ -78,6 +78,8 @@ def build_parser():
                    "lower = the same pixels in larger files for less host time)")
     p.add_argument("--fast_aux_png", action="store_true", help="samples/ and grid/ PNGs at zlib level 1 (same pixels, larger files); results/<id>.png keeps --png_level "
                    "(multi-GPU runs: the host's PNG encoding is what caps 8 processes per node)")
+    p.add_argument("--gpu_png", action="store_true", help="encode all six PNG files per image on the GPU (reface_amd/pngenc.py): the same pixels, other file "
+                   "bytes (about zlib level 1 in size), and the host only copies and writes the compressed bytes; not with --png_level / --fast_aux_png")
     p.add_argument("--gpu_prep", action="store_true", help="folder readers hand over uint8 arrays; normalise / mask / resize run on the GPU")
     return p
 
@@ -116,6 +118,9 @@ def main(argv=None):
     print(opt)
     if opt.laion400m or opt.Guidance:
         raise NotImplementedError("--laion400m / --Guidance are outside the REFace sampling path (SURVEY.md section 2)")
+    if opt.gpu_png and (opt.png_level is not None or opt.fast_aux_png or os.environ.get("RF_PNG_LEVEL")):
+        raise SystemExit("--gpu_png cannot be combined with --png_level / --fast_aux_png (or RF_PNG_LEVEL): the GPU encoder has one format, "
+                         "and the zlib levels belong to the host writer")
     torch.manual_seed(opt.seed)
     np.random.seed(opt.seed)
     rank = int(os.environ.get("RANK", "0"))
@@ -207,8 +212,12 @@ def main(argv=None):
         # probe's estimate is (5 x level-1 + 1 x level-6) / 6 of that -- see README "Known limits" for the 8-GPU host cap.
         lvl = os.environ.get("RF_PNG_LEVEL")
         level = int(lvl) if lvl else opt.png_level
+        png_encoder = None
+        if opt.gpu_png:          # (checked before the model was built: see main's first lines)
+            from reface_amd.pngenc import PngEncoder
+            png_encoder = PngEncoder(device)
         writer = OutputWriter(outpath, skip_grid=opt.skip_grid, threads=default_writer_threads(world), compress_level=level,
-                              aux_compress_level=1 if opt.fast_aux_png else None)
+                              aux_compress_level=1 if opt.fast_aux_png else None, png_encoder=png_encoder)
     host_compose = os.environ.get("RF_HOST_COMPOSE") == "1"          # debug: the reference's per-image float passes on the host (round-3 form)
     def with_landmark_prefetch(batches):
         """Yield (batch, landmarks136 or None): the dlib landmarks of batch i+1 are detected on a worker thread while the GPU works
@@ -286,6 +295,10 @@ def main(argv=None):
         dev = lambda t: t.to(device, non_blocking=True).float().contiguous()
         ops.compose_outputs_u8(x_img.contiguous(), dev(target), dev(inpaint), dev(mask), ref512.contiguous(), bufs["rec_dev"][:Bc],
                                with_grid=not opt.skip_grid)()
+        if opt.gpu_png:          # the encodes go right behind the compose kernel; their compressed bytes are fetched by the writer threads
+            jobs = writer.encode_device(bufs["rec_dev"][:Bc], H, W)
+            ev.record()
+            return {"png_jobs": jobs}
         bufs["rec_host"][:Bc].copy_(bufs["rec_dev"][:Bc], non_blocking=True)
         ev.record()
         return {"records": bufs["rec_host"][:Bc], "H": H, "W": W}
@@ -293,6 +306,9 @@ def main(argv=None):
     def flush(pending):
         """The batch whose copies were enqueued one iteration ago: wait for them, hand the arrays to the PNG writer threads."""
         ids, slot, out = pending
+        if "png_jobs" in out:          # (--gpu_png: no wait here at all -- every job carries its own event)
+            writer.submit_device(ids, out["png_jobs"])
+            return
         slot[1].synchronize()
         if "records" in out:
             writer.submit_u8(ids, out["records"].numpy(), out["H"], out["W"])
@@ -322,7 +338,7 @@ def main(argv=None):
             n_done += B
             n_batches += 1
             if not opt.skip_save:
-                if host_compose:
+                if host_compose and not opt.gpu_png:
                     out = stage_out(slot, {"x": x_img, "ref": runner.resized_reference(ref, opt.H, opt.W), "target": test_batch,
                                            "inpaint": kw_in["inpaint_image"], "mask": kw_in["inpaint_mask"]})
                 else:
