@@ -42,6 +42,8 @@ def build_parser():
     # ---- additions
     p.add_argument("--arcface_ckpt", type=str, default=DEFAULT_ARCFACE_CKPT,
                    help="(addition) ArcFace IR-SE50 weights; 'none' = the seeded weights the tests use")
+    p.add_argument("--gpu_png_decode", action="store_true",
+                   help="(addition) decode PNG files on the GPU (reface_amd/pngdec.py): the loader's workers only read bytes; the values are the same")
     p.add_argument("--json", type=str, default=None,
                    help="(addition) write top1, top5, mean, similarities, labels, image count and images/s (decode to scores; engine construction excluded) to this file")
     p.add_argument("--precision", type=str, choices=["full", "bf16"], default="full", help="(addition) precision of the ArcFace engine")
@@ -63,6 +65,9 @@ def main(argv=None):
             raise RuntimeError("Invalid path: %s" % p)
     print("Loading ResNet ArcFace")
     scorer = IDScorer(load_arcface_state(args.arcface_ckpt), precision=args.precision, batch=args.batch_size, device=device)
+    if args.gpu_png_decode:
+        from reface_amd.pngdec import PngDecoder
+        scorer.png_decoder = PngDecoder(device)
     r = scorer.score_folders(args.path, dataset=args.dataset, num_workers=num_workers)
     print("Top-1 accuracy: {:.2f}%".format(r["top1"] * 100))
     print("Top-5 accuracy: {:.2f}%".format(r["top5"] * 100))
@@ -76,6 +81,9 @@ def main(argv=None):
             json.dump({"top1": r["top1"], "top5": r["top5"], "mean": r["mean"], "similarities": [float(s) for s in r["similarities"]],
                        "labels": r["labels"], "rank": [int(k) for k in r["rank"]], "pred": [int(k) for k in r["pred"]], "images": r["images"],
                        "images_per_s": r["images_per_s"], "seconds": r["seconds"], "precision": args.precision, "dataset": args.dataset}, f)
+    if args.gpu_png_decode:          # (stderr: the printed lines stay what they are without the flag)
+        from reface_amd.pngdec import counts_line
+        print(counts_line(scorer.png_decoder), file=sys.stderr)
     return r
 
 

@@ -32,6 +32,8 @@ def build_parser():
                    help="target images, results")
     # ---- additions
     p.add_argument("--hopenet_ckpt", type=str, default=DEFAULT_HOPENET_CKPT, help="(addition) Hopenet weights; 'none' = the seeded weights the tests use")
+    p.add_argument("--gpu_png_decode", action="store_true",
+                   help="(addition) decode PNG files on the GPU (reface_amd/pngdec.py): the loader's workers only read bytes; the values are the same")
     p.add_argument("--json", type=str, default=None,
                    help="(addition) write Pose_value, distances, labels, degrees, image count and images/s (decode to score; engine construction excluded) to this file")
     return p
@@ -52,6 +54,9 @@ def main(argv=None):
             raise SystemExit(f"pose_compare: {p}: .npz statistics are not supported (the reference's .npz branch cannot run)")
     print("Loading hopenet")
     scorer = PoseScorer(load_hopenet_state(args.hopenet_ckpt), batch=args.batch_size, device=device)
+    if args.gpu_png_decode:
+        from reface_amd.pngdec import PngDecoder
+        scorer.png_decoder = PngDecoder(device)
     r = scorer.score_folders(args.path, num_workers=num_workers)
     print("Pose_value: ", r["pose_value"])
     if args.json:
@@ -59,6 +64,9 @@ def main(argv=None):
             json.dump({"pose_value": r["pose_value"], "distances": [float(d) for d in r["distances"]], "labels": r["labels"],
                        "degrees_target": r["degrees_target"].tolist(), "degrees_result": r["degrees_result"].tolist(), "images": r["images"],
                        "images_per_s": r["images_per_s"], "seconds": r["seconds"]}, f)
+    if args.gpu_png_decode:          # (stderr: the printed lines stay what they are without the flag)
+        from reface_amd.pngdec import counts_line
+        print(counts_line(scorer.png_decoder), file=sys.stderr)
     return r
 
 

@@ -36,6 +36,8 @@ def build_parser():
     p.add_argument("--clip_ckpt", type=str, default=DEFAULT_CLIP_CKPT,
                    help="(addition) the ViT-B/32 file clip.load caches (TorchScript archive or state dict); 'none' = the seeded tower the tests use")
     p.add_argument("--precision", type=str, default="full", choices=["full", "bf16"], help="(addition) tower arithmetic: fp32, or bf16 operands")
+    p.add_argument("--gpu_png_decode", action="store_true",
+                   help="(addition) decode PNG files on the GPU (reface_amd/pngdec.py): the loader's workers only read bytes; the values are the same")
     p.add_argument("--json", type=str, default=None,
                    help="(addition) write the value, its four terms, image counts, images/s (decode to value; engine construction excluded) and the "
                         "number of images prepared on the host to this file")
@@ -57,6 +59,9 @@ def main(argv=None):
             raise RuntimeError("Invalid path: %s" % p)
     state, _ = load_fid_clip_state(args.clip_ckpt)
     scorer = FidScorer(state, precision=args.precision, batch=args.batch_size, device=device)
+    if args.gpu_png_decode:
+        from reface_amd.pngdec import PngDecoder
+        scorer.png_decoder = PngDecoder(device)
     r = scorer.score_folders(args.path, num_workers=num_workers)
     fid_value = r["fid"]
     print("FID: ", fid_value)
@@ -66,6 +71,9 @@ def main(argv=None):
         with open(args.json, "w") as f:
             json.dump({k: r[k] for k in ("fid", "mean_term", "trace1", "trace2", "trace_covmean", "images1", "images2", "images", "host_prepared",
                                          "images_per_s", "seconds")} | {"precision": args.precision}, f)
+    if args.gpu_png_decode:          # (stderr: the printed lines stay what they are without the flag)
+        from reface_amd.pngdec import counts_line
+        print(counts_line(scorer.png_decoder), file=sys.stderr)
     return r
 
 

@@ -34,6 +34,8 @@ def build_parser():
     p.add_argument("--lpips_ckpt", type=str, default="models/REFace/checkpoints/last.ckpt",
                    help="LPIPS weights: a state dict of the module or a REFace checkpoint with lpips_loss.* keys; 'none' = the seeded weights the tests use")
     p.add_argument("--print_sim", type=bool, default=False, help="also print one distance per result (any non-empty string is true)")
+    p.add_argument("--gpu_png_decode", action="store_true",
+                   help="(addition) decode PNG files on the GPU (reface_amd/pngdec.py): the loader's workers only read bytes; the values are the same")
     p.add_argument("--json", type=str, default=None,
                    help="write LPIPS_value, distances, labels, image count and images/s (decode to score; engine construction excluded) to this file")
     return p
@@ -61,6 +63,9 @@ def main(argv=None):
     state = load_lpips_state(args.lpips_ckpt, args.net)
     print("Loading LPIPS(%s) from %s" % (args.net, args.lpips_ckpt))
     scorer = LPIPSScorer(state, net=args.net, batch=args.batch_size, device=device)
+    if args.gpu_png_decode:
+        from reface_amd.pngdec import PngDecoder
+        scorer.png_decoder = PngDecoder(device)
     try:
         r = scorer.score_folders(args.path, num_workers=num_workers)
     except ValueError as e:          # a result whose size differs from its target's, an image too small for the net
@@ -74,6 +79,9 @@ def main(argv=None):
         with open(args.json, "w") as f:
             json.dump({"lpips_value": r["lpips_value"], "distances": [float(d) for d in r["distances"]],
                        "labels": r["labels"], "net": args.net, "images": r["images"], "images_per_s": r["images_per_s"], "seconds": r["seconds"]}, f)
+    if args.gpu_png_decode:          # (stderr: the printed lines stay what they are without the flag)
+        from reface_amd.pngdec import counts_line
+        print(counts_line(scorer.png_decoder), file=sys.stderr)
     return r
 
 

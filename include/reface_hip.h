@@ -645,6 +645,38 @@ int rf_png_deflate_segments(const void* streams_u8, int B, int64_t n, int64_t st
 int rf_png_pack(const void* slots_u8, const int* seg_bytes, const uint32_t* seg_adler, int B, int64_t n, void* out_u8, int64_t out_stride,
                 int* lengths, void* stream);
 
+/*
+ * PNG decoding on the device (the callers' --gpu_png_decode; reface_amd/pngdec.py parses the chunks, uploads the IDAT bytes and raises the
+ * error codes).  A batch is described by RF_PNGDEC_DESC int64 words per file, given twice: desc_host (read and range-checked by the entry
+ * point before anything is launched) and desc (the same words in device memory, read by the kernels):
+ *   0 comp_off, 1 comp_len   the file's zlib stream at comp + comp_off
+ *   2 filt_off, 3 expect     its filtered stream at filt + filt_off (a multiple of 16); expect = H * (1 + W * bpp)
+ *   4 H, 5 W, 6 bpp          bpp = 1 | 2 | 3 | 4 bytes per pixel (grey, grey + alpha, RGB, RGBA; 8 bits per sample, not interlaced)
+ *   7 out_c                  channels written: bpp, or 1 | 3 from grey (+ alpha: dropped; the sample is replicated), or 3 from RGBA
+ *   8 pix_off, 9 row_stride  the image's pixels at pix + pix_off, row y at + y * row_stride bytes
+ *   10 cand_begin, 11 cand_count   the file's candidate piece starts: cand[cand_begin ...]; 0, or the stream start (offset 2) and the rest
+ * status is int32 [B, 2]: the error code (0 = none; the codes of csrc/png_inflate.h) and the inflate plan taken (0 serial, 1 segments).
+ *   rf_png_inflate     : zlib streams -> filtered streams.  Every read is bounded by comp_len, every write by expect, every distance by the
+ *                        bytes produced so far; a damaged stream leaves an error code.  Serial plan: one wave per stream, the Huffman
+ *                        symbols walked on wave-uniform values, the 32 KiB window and the tables in LDS, matches and stored blocks copied
+ *                        by the whole wave.  Segmented plan, tried for files with cand_count >= 2: cand is int32 [2, ncand] (the file of
+ *                        each candidate, ascending; then its offset in the file's stream, ascending per file; cand_host = the same words
+ *                        on the host); one wave decodes each candidate into slots u8 [ncand, 32768] (16-byte aligned) up to an empty
+ *                        stored block, a stored block that fills the slot, or the final block, and leaves pieces int32 [ncand, 5]
+ *                        (end offset, bytes, Adler-32 partial as in rf_png_deflate_segments, flags, place in the chain).  A file is
+ *                        taken from its pieces only if they chain up from offset 2 exactly: each usable (no error, no reference before its
+ *                        own start), each but the last of 32768 bytes, each end offset a candidate, the total = expect and the combined
+ *                        Adler-32 = the trailer; otherwise the serial kernel, enqueued behind, decodes it.  Candidates are hints only.
+ *   rf_png_unfilter_u8 : filtered streams -> pixels (None / Sub / Up / Average / Paeth undone in exact integer arithmetic), one wave per
+ *                        image, W <= 8192, H <= 2^20.  Files whose error code is set are skipped; a filter byte above 4 sets code 11.  status must
+ *                        have been written by rf_png_inflate (or zeroed).
+ */
+#define RF_PNGDEC_DESC 12
+int rf_png_inflate(const void* comp_u8, int64_t comp_bytes, const int64_t* desc_host, const int64_t* desc, int B, void* filt_u8, int64_t filt_bytes,
+                   const int* cand_host, const int* cand, int ncand, void* slots_u8, int* pieces, int* status, void* stream);
+int rf_png_unfilter_u8(const void* filt_u8, int64_t filt_bytes, const int64_t* desc_host, const int64_t* desc, int B, void* pix_u8, int64_t pix_bytes,
+                       int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

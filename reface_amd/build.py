@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libreface_hip.so")
-SOURCES = ["gemm.hip", "gemm_f16.hip", "norm.hip", "attention.hip", "elementwise.hip", "encoder.hip", "ffn.hip", "smallconv.hip", "attnin.hip", "parsing.hip", "pasteback.hip", "align.hip", "video_prep.hip", "idscore.hip", "pose.hip", "expr.hip", "fid.hip", "lpips.hip", "pngenc.hip"]
+SOURCES = ["gemm.hip", "gemm_f16.hip", "norm.hip", "attention.hip", "elementwise.hip", "encoder.hip", "ffn.hip", "smallconv.hip", "attnin.hip", "parsing.hip", "pasteback.hip", "align.hip", "video_prep.hip", "idscore.hip", "pose.hip", "expr.hip", "fid.hip", "lpips.hip", "pngenc.hip", "pngdec.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
 # per-file extras.  attention: keep MFMA accumulators in VGPRs -- the online softmax reads every score and rescales O each
 # tile, and with AGPR accumulators hipcc emitted ~160 v_accvgpr_read/write per KV tile (40 % of the loop's VALU work).
@@ -26,7 +26,9 @@ HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(os.path.dirname(HERE), "
 UNIT_DEPS = {"gemm_f16.hip": [os.path.join(CSRC, "gemm.hip")], "pasteback.hip": [os.path.join(CSRC, "pil_u8.h")], "align.hip": [os.path.join(CSRC, "pil_u8.h")],
              "video_prep.hip": [os.path.join(CSRC, "pil_u8.h")], "elementwise.hip": [os.path.join(CSRC, "cv_u8.h")],
              "idscore.hip": [os.path.join(CSRC, "cv_u8.h")], "expr.hip": [os.path.join(CSRC, "pil_u8.h")],
-             "fid.hip": [os.path.join(CSRC, "pil_u8.h")]}
+             "fid.hip": [os.path.join(CSRC, "pil_u8.h")],
+             # png_inflate.h: the zlib decoder core, compiled by hipcc here and by a host compiler into tests/pngdec_host_main.cpp
+             "pngdec.hip": [os.path.join(CSRC, "png_inflate.h")]}
 
 
 

@@ -213,6 +213,7 @@ class ExprScorer:
         self.add_relu = bool(add_relu)
         self.sd = check_recon_state(state_dict)
         self._engines = {}
+        self.png_decoder = None          # a pngdec.PngDecoder: the folders' files are then decoded on the device (--gpu_png_decode)
         self._taps = {}
 
     def engine(self, B):
@@ -298,8 +299,12 @@ class ExprScorer:
             raise ValueError(f"no image files in {folder}")
         labels = parse_labels_first(files)
         batch = min(self.batch, len(files))          # (:168-171: a batch larger than the folder becomes the folder)
-        loader = torch.utils.data.DataLoader(_ImageFolder(files), batch_size=batch, shuffle=False, drop_last=False, num_workers=num_workers,
-                                             collate_fn=_list_collate)
+        if self.png_decoder is not None:
+            from . import pngdec
+            loader = pngdec.device_batches(self.png_decoder, files, batch, num_workers, "RGB")
+        else:
+            loader = torch.utils.data.DataLoader(_ImageFolder(files), batch_size=batch, shuffle=False, drop_last=False, num_workers=num_workers,
+                                                 collate_fn=_list_collate)
         coef = torch.empty((len(files), N_COEF), dtype=F32, device=self.dev)
         at = 0
         for imgs in loader:

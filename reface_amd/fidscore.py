@@ -327,14 +327,23 @@ class _FidFolder(torch.utils.data.Dataset):
     everywhere (alpha dropped) -- for these the bytes PIL resizes in the image's own mode and then converts are the bytes of the RGB image
     resized -- and ("host", fp32 [3, 224, 224] from ``prep_host``) for every other mode or alpha."""
 
-    def __init__(self, files):
-        self.files = files
+    def __init__(self, files, gpu_png=False):
+        self.files, self.gpu_png = files, gpu_png
 
     def __len__(self):
         return len(self.files)
 
     def __getitem__(self, i):
         from PIL import Image
+        if self.gpu_png:
+            # --gpu_png_decode: RGB and grey PNG files travel as bytes, ("png", bytes), and are decoded on the device as
+            # .convert("RGB") -- the "u8" cases above that need no look at the pixels; RGBA (alpha must be inspected) stays here
+            from . import pngdec
+            with open(self.files[i], "rb") as f:
+                data = f.read()
+            info = pngdec.parse_png(data)
+            if info.route == "gpu" and info.bpp in (1, 3):
+                return "png", data
         return decode_item(Image.open(self.files[i]))
 
 
@@ -373,6 +382,7 @@ class FidScorer:
         self.dim = self.cfg.proj
         self._engines = {}
         self._taps = {}
+        self.png_decoder = None          # a pngdec.PngDecoder: RGB and grey PNG files are then decoded on the device (--gpu_png_decode)
 
     def engine(self, B):
         eng = self._engines.get(B)
@@ -459,12 +469,16 @@ class FidScorer:
         if not files:
             raise ValueError(f"no image files in {folder}")
         batch = effective_batch(self.batch, len(files))
-        loader = torch.utils.data.DataLoader(_FidFolder(files), batch_size=batch, shuffle=False, drop_last=False, num_workers=num_workers,
-                                             collate_fn=_list_collate)
+        loader = torch.utils.data.DataLoader(_FidFolder(files, self.png_decoder is not None), batch_size=batch, shuffle=False, drop_last=False,
+                                             num_workers=num_workers, collate_fn=_list_collate)
         feat = torch.empty((len(files), self.dim), dtype=F32, device=self.dev)
         at = host = 0
         for items in loader:
             n = len(items)
+            png = [k for k, (kind, _) in enumerate(items) if kind == "png"]
+            if png:
+                for k, t in zip(png, self.png_decoder.decode([items[k][1] for k in png], "RGB")):
+                    items[k] = ("u8", t)
             feat[at:at + n] = self.features_items(items)
             host += sum(1 for kind, _ in items if kind == "host")
             at += n

@@ -136,6 +136,21 @@ class _PairFolder(torch.utils.data.Dataset):
         return torch.from_numpy(img.copy()), torch.from_numpy(lab.copy())
 
 
+class _PairBytes(torch.utils.data.Dataset):
+    """``_PairFolder`` for --gpu_png_decode: (image item, label-map item) as ``pngdec.ByteFolder`` gives them (file bytes where the device
+    decodes the file, PIL's array where it does not)."""
+
+    def __init__(self, files, maskfiles):
+        from . import pngdec
+        self.img, self.lab = pngdec.ByteFolder(files, "RGB"), pngdec.ByteFolder(maskfiles[:len(files)], "L")
+
+    def __len__(self):
+        return len(self.img)
+
+    def __getitem__(self, i):
+        return self.img[i], self.lab[i]
+
+
 class IDScorer:
     """ArcFace identity scoring on the GPU.  ``state_dict``: IR-SE50 weights (model_ir_se50.pth layout); ``precision``: "full" (fp32, the
     default: this is a measurement) or "bf16" for the ArcFace engine; ``batch``: images per engine run (engines are built per batch size:
@@ -155,6 +170,7 @@ class IDScorer:
         self.net.load_state_dict(state_dict, strict=True)
         self.net.to(self.dev).eval()
         self._luts = {}
+        self.png_decoder = None          # a pngdec.PngDecoder: images and label maps are then decoded on the device (--gpu_png_decode)
 
     def lut(self, preserve):
         key = tuple(sorted(int(p) for p in preserve))
@@ -231,8 +247,18 @@ class IDScorer:
             raise ValueError(f"no image files in {folder}")
         labels = parse_labels(files)
         batch = min(self.batch, len(files))          # (:273-276: a batch larger than the folder becomes the folder)
-        loader = torch.utils.data.DataLoader(_PairFolder(files, maskfiles), batch_size=batch, shuffle=False, drop_last=False,
-                                             num_workers=num_workers, collate_fn=raw_collate)
+        if self.png_decoder is not None:
+            # the workers read bytes; images (.convert("RGB")) and label maps (.convert("L")) are decoded here, on the device
+            from . import pngdec
+            if len(maskfiles) < len(files):
+                raise ValueError(f"{len(files)} images but only {len(maskfiles)} label maps")
+            dec = self.png_decoder
+            pairs = torch.utils.data.DataLoader(_PairBytes(files, maskfiles), batch_size=batch, shuffle=False, drop_last=False, num_workers=num_workers,
+                                                collate_fn=pngdec.list_collate)
+            loader = ((dec.decode([a for a, _ in items], "RGB"), [m[:, :, 0] for m in dec.decode([b for _, b in items], "L")]) for items in pairs)
+        else:
+            loader = torch.utils.data.DataLoader(_PairFolder(files, maskfiles), batch_size=batch, shuffle=False, drop_last=False,
+                                                 num_workers=num_workers, collate_fn=raw_collate)
         feats = torch.empty((len(files), 512), dtype=torch.float32, device=self.dev)
         at = 0
         for img, lab in loader:

@@ -271,8 +271,9 @@ def _pairs_collate(items):
 class _PairFolder(torch.utils.data.Dataset):
     """(target bytes, result bytes) of every result, the target picked by the result's label."""
 
-    def __init__(self, targets, results, labels):
-        self.t, self.r, self.labels = _ImageFolder(targets), _ImageFolder(results), labels
+    def __init__(self, targets, results, labels, folder=None):
+        folder = folder or _ImageFolder          # (--gpu_png_decode: pngdec.ByteFolder, whose items are file bytes)
+        self.t, self.r, self.labels = folder(targets), folder(results), labels
 
     def __len__(self):
         return len(self.r)
@@ -315,6 +316,7 @@ class LPIPSScorer:
             raise ValueError(f"batch must be positive, not {batch}")
         self.sd = check_lpips_state(state_dict, net)
         self._engines = collections.OrderedDict()
+        self.png_decoder = None          # a pngdec.PngDecoder: the folders' files are then decoded on the device (--gpu_png_decode)
 
     def step(self, hw):
         """Pairs per engine run for images of size ``hw``."""
@@ -440,11 +442,20 @@ class LPIPSScorer:
         vals = torch.empty((len(results), N_TAPS), dtype=F64, device=self.dev)
         torch.cuda.synchronize(self.dev)
         t0 = time.perf_counter()
-        loader = torch.utils.data.DataLoader(_PairFolder(targets, results, labels), batch_sampler=[list(range(a, b)) for a, b in chunks],
+        dec = self.png_decoder
+        folder = None
+        if dec is not None:
+            from . import pngdec
+            folder = lambda files: pngdec.ByteFolder(files, "RGB")          # noqa: E731
+        loader = torch.utils.data.DataLoader(_PairFolder(targets, results, labels, folder), batch_sampler=[list(range(a, b)) for a, b in chunks],
                                              num_workers=num_workers, collate_fn=_pairs_collate)
         with torch.no_grad():
             for (a, b), items in zip(chunks, loader):
-                self._run([t for t, _ in items], [r for _, r in items], shapes[a], self._prep_u8, vals[a:b])
+                ts, rs = [t for t, _ in items], [r for _, r in items]
+                if dec is not None:          # the workers read bytes: both sides of the chunk are decoded on the device in one batch
+                    outs = dec.decode(ts + rs, "RGB")
+                    ts, rs = outs[:len(ts)], outs[len(ts):]
+                self._run(ts, rs, shapes[a], self._prep_u8, vals[a:b])
             d, totals = self._finish(vals)
         t = totals.cpu().numpy()
         torch.cuda.synchronize(self.dev)

@@ -61,6 +61,23 @@ def load_frame(frames_dir, sid):
     return np.asarray(im, dtype=np.uint8)
 
 
+def frame_item(frames_dir, sid):
+    """What a loader hands to ``pngdec.PngDecoder.decode`` for frame ``sid`` (--gpu_png_decode): the file's bytes where the device decodes it
+    to what ``load_frame`` gives (8-bit RGB and RGBA files), else ``load_frame``'s array as a host tensor."""
+    from . import pngdec
+    with open(os.path.join(frames_dir, f"{int(sid)}.png"), "rb") as f:
+        data = f.read()
+    info = pngdec.parse_png(data)
+    if info.route == "gpu" and info.bpp in (3, 4):
+        return data
+    return torch.from_numpy(np.array(load_frame(frames_dir, sid)))
+
+
+def load_frames_device(decoder, frames_dir, sids):
+    """``load_frame`` of every id as uint8 device tensors [H, W, 3 | 4], decoded on the device."""
+    return decoder.decode([frame_item(frames_dir, sid) for sid in sids])
+
+
 def paste_on_device(result01, coeffs, frames, crop_size=CROP_SIZE, channels=4):
     """The device half of stage 3 for frames that are on the device already: run_batch's fp32 [B, 3, h, w] result, the frames' inverse
     transforms (fp64 [B, 8], host) and B uint8 device tensors [H, W, 3 | 4] (sizes and channel counts may differ within the batch) ->

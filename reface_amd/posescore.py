@@ -209,6 +209,7 @@ class PoseScorer:
             raise ValueError(f"batch must be positive, not {batch}")
         self.sd = check_hopenet_state(state_dict)
         self._engines = {}
+        self.png_decoder = None          # a pngdec.PngDecoder: the folders' files are then decoded on the device (--gpu_png_decode)
 
     def engine(self, B):
         eng = self._engines.get(B)
@@ -276,8 +277,12 @@ class PoseScorer:
             raise ValueError(f"no image files in {folder}")
         labels = parse_labels_last(files)
         batch = min(self.batch, len(files))          # (:131-134: a batch larger than the folder becomes the folder)
-        loader = torch.utils.data.DataLoader(_ImageFolder(files), batch_size=batch, shuffle=False, drop_last=False, num_workers=num_workers,
-                                             collate_fn=_list_collate)
+        if self.png_decoder is not None:
+            from . import pngdec
+            loader = pngdec.device_batches(self.png_decoder, files, batch, num_workers, "RGB")
+        else:
+            loader = torch.utils.data.DataLoader(_ImageFolder(files), batch_size=batch, shuffle=False, drop_last=False, num_workers=num_workers,
+                                                 collate_fn=_list_collate)
         deg = torch.empty((len(files), 3), dtype=F32, device=self.dev)
         at = 0
         for imgs in loader:

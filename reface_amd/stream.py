@@ -27,14 +27,21 @@ class FrameDataset(Dataset):
     """The host half of the stream: frame ``<frames_dir>/<i>.png`` decoded to a uint8 [H, W, 3 | 4] tensor, with the dataset's 12-digit id.
     Collate with ``reface_amd.data.raw_collate``: frames of one size are stacked, frames of different sizes stay a list."""
 
-    def __init__(self, frames_dir, n):
-        self.frames_dir, self.n = frames_dir, int(n)
+    def __init__(self, frames_dir, n, raw=False):
+        self.frames_dir, self.n, self.raw = frames_dir, int(n), raw
 
     def __len__(self):
         return self.n
 
     def __getitem__(self, i):
+        if self.raw:          # --gpu_png_decode: the file's bytes (pasteback.frame_item); collate with ``frame_items_collate``
+            from .pasteback import frame_item
+            return frame_item(self.frames_dir, i), str(i).zfill(12)
         return torch.from_numpy(np.array(load_frame(self.frames_dir, i))), str(i).zfill(12)
+
+
+def frame_items_collate(items):
+    return [f for f, _ in items], [i for _, i in items]
 
 
 def keep_lut(labels):

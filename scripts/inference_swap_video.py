@@ -121,6 +121,8 @@ def build_parser():
     p.add_argument("--stream", action="store_true", help="raw frames to pasted frames as one device-resident chain: the work of --align --parse_masks "
                    "--paste_back with one PNG decode and one encode per frame and no intermediate files (reads what they read; writes results/, "
                    "<video>_inv_transforms.npy and temp_results/)")
+    p.add_argument("--gpu_png_decode", action="store_true", help="--paste_back / --stream: decode the video's frames on the GPU "
+                   "(reface_amd/pngdec.py) and hand them to the device chain as device tensors; the files written are the same")
     p.add_argument("--gpu_png", action="store_true", help="--paste_back / --stream: encode the pasted RGBA frames of results/ on the GPU "
                    "(reface_amd/pngenc.py): the same pixels, other file bytes (about zlib level 1 in size); crops, label maps and model_outputs "
                    "stay on the host writer")
@@ -231,7 +233,7 @@ def load_model_and_sampler(opt, config):
 def run_stream(opt):
     """--stream: frames -> pasted frames with every intermediate on the device (reface_amd/stream.py)."""
     from reface_amd.data import load_source_reference, raw_collate
-    from reface_amd.stream import FrameDataset, VideoStream, stream_paths
+    from reface_amd.stream import FrameDataset, VideoStream, frame_items_collate, stream_paths
     paths, lm, src_lm = check_align_inputs(opt)
     config = rcfg.load(opt.config)
     test_args = dict(config.data.params.test.params)
@@ -260,9 +262,10 @@ def run_stream(opt):
         os.makedirs(d, exist_ok=True)
     ref1 = load_source_reference(pp["src"], pp["src_mask"], test_args["preserve_mask_src_FFHQ"]).to(device)
     ns = max(1, opt.n_samples)
-    ds = FrameDataset(sp["video_frames"], len(paths) // ns * ns)          # drop_last: the trailing partial batch is never swapped, so never decoded
+    ds = FrameDataset(sp["video_frames"], len(paths) // ns * ns, raw=opt.gpu_png_decode)          # drop_last: the trailing partial batch is never swapped, so never decoded
     loader = torch.utils.data.DataLoader(ds, batch_size=ns, num_workers=opt.num_workers, pin_memory=True, shuffle=False, drop_last=True,
-                                         collate_fn=raw_collate)
+                                         collate_fn=frame_items_collate if opt.gpu_png_decode else raw_collate)
+    decoder = make_png_decoder(opt, device)
     start_code = None
     if opt.fixed_code:
         start_code = torch.randn([opt.C, opt.H // opt.f, opt.W // opt.f], device=device).unsqueeze(0).repeat(opt.n_samples, 1, 1, 1)
@@ -271,6 +274,10 @@ def run_stream(opt):
     held = []          # --gpu_png: the previous batch's enqueued encodes, handed to the writer only after this batch has been enqueued
     with torch.no_grad(), model.ema_scope():
         for frames, ids in loader:          # (the iterator draws its base seed from the CPU generator, as the staged loader's does)
+            if decoder is not None:          # the workers read bytes: the frames are decoded here, on the device
+                job = decoder.decode_async(frames)
+                frames = job.result()
+                frames = job.batch if job.batch is not None else frames
             test_batch, kw, state = vs.prepare(frames, ids)
             if opt.Start_from_target:
                 start_code = runner.start_from_target(test_batch)
@@ -295,6 +302,9 @@ def run_stream(opt):
     torch.cuda.synchronize()
     n_files = writer.close() if writer is not None else 0
     n_pasted = n_files // 4 if keep else n_files
+    if decoder is not None:
+        from reface_amd.pngdec import counts_line
+        print("inference_swap_video --" + counts_line(decoder, "frames"))
     left = len(paths) - n_done
     print(f"inference_swap_video --stream: {n_done} of {len(paths)} frames swapped and pasted on the device"
           + (f" ({left} trailing frames are not swapped: drop_last)" if left else "") + f"; {n_pasted} pasted frames written to {results}, inverse "
@@ -303,6 +313,14 @@ def run_stream(opt):
              "no crops, label maps or model_outputs files were written (--stream_keep writes them)")
           + " (the mp4 + audio mux of the reference's stage 3 is not built).")
     return n_done
+
+
+def make_png_decoder(opt, device):
+    """--gpu_png_decode: the device PNG decoder the video's frames come through (None: PIL in the loader)."""
+    if not opt.gpu_png_decode:
+        return None
+    from reface_amd.pngdec import PngDecoder
+    return PngDecoder(device)
 
 
 def make_png_encoder(opt, device):
@@ -326,6 +344,9 @@ def main(argv=None):
     if opt.gpu_png and not (opt.paste_back or opt.stream or opt.stream_keep):
         raise SystemExit("inference_swap_video: --gpu_png encodes the pasted frames of results/ and needs --paste_back or --stream "
                          "(model_outputs/ stays on the host writer)")
+    if opt.gpu_png_decode and not (opt.paste_back or opt.stream or opt.stream_keep):
+        raise SystemExit("inference_swap_video: --gpu_png_decode decodes the video's frames for --paste_back or --stream; without either no frame "
+                         "is read (the crops of target_frames/ go through the dataset's host transforms)")
     if opt.gpu_png and opt.skip_save:
         print("inference_swap_video: --skip_save writes no files, so --gpu_png has nothing to encode")
     if opt.stream or opt.stream_keep:
@@ -381,10 +402,11 @@ def main(argv=None):
         from reface_amd.pasteback import PasteBack, PngWriter
         sp = pasteback_paths(opt)
         paster, writer = PasteBack(sp["video_frames"], sp["inv_transforms"]), PngWriter(png_encoder=make_png_encoder(opt, device))
+    decoder = make_png_decoder(opt, device) if paster is not None else None
     held = []
     with torch.no_grad(), model.ema_scope():
         for test_batch, prior, kw, ids in loader:
-            frames = paster.prefetch(ids) if paster is not None else None          # decoded on the pool while the batch samples
+            frames = paster.prefetch(ids) if paster is not None and decoder is None else None          # decoded on the pool while the batch samples
             if opt.Start_from_target:
                 start_code = runner.start_from_target(test_batch)        # `use_prior = False` (:555)
             kw = {n: kw[n].to(device, non_blocking=True) for n in kw}
@@ -396,8 +418,16 @@ def main(argv=None):
             res = x_img.cpu().numpy()
             for i, sid in enumerate(ids):
                 Image.fromarray(O.to_u8_hwc(res[i])).resize((1024, 1024), Image.BILINEAR).save(os.path.join(model_out, sid + ".png"))
-            if paster is not None and opt.gpu_png:          # the pasted frames stay on the device and are encoded there
-                dev_frames = [torch.from_numpy(np.array(f.result(), copy=True)).to(device) for f in frames]
+            if paster is not None and decoder is not None and not opt.gpu_png:          # frames decoded and pasted on the device, encoded on the host
+                from reface_amd.pasteback import load_frames_device
+                for sid, frame in zip(ids, paster.paste_device(x_img, ids, load_frames_device(decoder, sp["video_frames"], ids))):
+                    writer.submit(os.path.join(opt.outdir, "results", sid + ".png"), frame.cpu().numpy())
+            elif paster is not None and opt.gpu_png:          # the pasted frames stay on the device and are encoded there
+                if decoder is not None:
+                    from reface_amd.pasteback import load_frames_device
+                    dev_frames = load_frames_device(decoder, sp["video_frames"], ids)
+                else:
+                    dev_frames = [torch.from_numpy(np.array(f.result(), copy=True)).to(device) for f in frames]
                 pasted = paster.paste_device(x_img, ids, dev_frames)
                 held = hand_over(writer, held, [([os.path.join(opt.outdir, "results", ids[i] + ".png") for i in idx], job)
                                                 for idx, job in writer.encode_device(pasted)])
@@ -410,6 +440,9 @@ def main(argv=None):
     if paster is not None:
         paster.close()
         n_pasted = writer.close()
+        if decoder is not None:
+            from reface_amd.pngdec import counts_line
+            print("inference_swap_video --" + counts_line(decoder, "frames"))
         print(f"Swapped crops of {n_done} frames are in {model_out}; {n_pasted} pasted frames are in {os.path.join(opt.outdir, 'results')} "
               f"(the mp4 + audio mux of the reference's stage 3 is not built).")
     else:
