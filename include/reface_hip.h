@@ -677,6 +677,39 @@ int rf_png_inflate(const void* comp_u8, int64_t comp_bytes, const int64_t* desc_
 int rf_png_unfilter_u8(const void* filt_u8, int64_t filt_bytes, const int64_t* desc_host, const int64_t* desc, int B, void* pix_u8, int64_t pix_bytes,
                        int* status, void* stream);
 
+/*
+ * Baseline JPEG encoding of device-resident images (scripts/inference_swap_video.py --write_video; reface_amd/mjpeg.py puts SOI .. SOS in
+ * front of the result).  All arithmetic is 32-bit integer and restates libjpeg's: the scan is byte for byte the one libjpeg writes with the
+ * same tables and one restart interval per MCU row.  subsampling is 420 (MCU 16 x 16: Y00 Y01 Y10 Y11 Cb Cr) or 444 (MCU 8 x 8: Y Cb Cr);
+ * mcu_rows = ceil(H / MCU height), mcus = ceil(W / MCU width), nbr = mcus * blocks per MCU.  1 <= H, W <= 65535.
+ *   rf_jpeg_blocks_u8 : images u8 [B, H, W, C], C = 3 | 4 (the 4th byte is ignored; image b at images + b * image_stride, row y at
+ *                       + y * row_stride bytes) -> coef int16 [B, mcu_rows, 64, nbr]: element [z][j] of a tile is the quantised
+ *                       coefficient at zigzag position z of block j of the MCU row, blocks in scan order -- coefficient-major, so that
+ *                       the one-lane-per-block kernels on both sides touch it coalesced.  rgb_ycc_convert (16-bit fixed point), every
+ *                       component edge-replicated to its size in blocks; at 420 the full-resolution chroma is edge-replicated, averaged
+ *                       over 2 x 2 with the bias 1 (even output columns) / 2 (odd), and the downsampled plane's last row replicated down;
+ *                       jfdctint ("islow", CONST_BITS 13, PASS1_BITS 2) on samples - 128; c = sign(d) * ((|d| + 4 q) / (8 q)).  quant is
+ *                       int32 [2, 64] on the device: the luma and chroma tables in zigzag order.  Dummy blocks (past a component's size
+ *                       in blocks, inside the last MCU column / row) carry the DC of the block before them in the MCU and no AC.
+ *   rf_jpeg_entropy   : coef -> slots u8 [B, mcu_rows, slot_stride] and seg_bytes int32 [B, mcu_rows]: every MCU row is one restart
+ *                       interval, coded from DC predictors of 0: DC difference category + amplitude bits, AC (run, size) symbols with ZRL
+ *                       and EOB, bits most significant first, 00 behind every FF byte, the tail padded with 1-bits.  huff is uint32
+ *                       [2, 272] on the device: per table class (luma, chroma) 16 DC then 256 AC entries, (code << 5) | length.
+ *                       slot_stride >= RF_JPEG_SLOT(nbr), the bound for ANY coefficients and tables (values are clamped to the 8-bit
+ *                       range of categories, lengths to 16): no input overflows a slot.
+ *   rf_jpeg_pack      : -> out u8 (image b at out + b * out_stride, out_stride >= mcu_rows * (slot_stride + 2), below 2^31): the intervals
+ *                       back to back, FF D0+(i mod 8) behind interval i, FF D9 behind the last; lengths int32 [B] = the bytes written.
+ */
+#define RF_JPEG_BLOCK_BITS (64 * 27)
+#define RF_JPEG_SLOT(nbr) (2 * (((int64_t)(nbr) * RF_JPEG_BLOCK_BITS + 7) / 8 + 1))
+#define RF_JPEG_HUFF_WORDS (2 * 272)
+int rf_jpeg_blocks_u8(const void* images_u8, int B, int H, int W, int C, int64_t image_stride, int64_t row_stride, int subsampling, const int* quant,
+                      int16_t* coef, void* stream);
+int rf_jpeg_entropy(const int16_t* coef, int B, int mcu_rows, int mcus, int subsampling, const uint32_t* huff, void* slots_u8, int64_t slot_stride,
+                    int* seg_bytes, void* stream);
+int rf_jpeg_pack(const void* slots_u8, int64_t slot_stride, const int* seg_bytes, int B, int mcu_rows, void* out_u8, int64_t out_stride, int* lengths,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,10 @@ thread.  It reads what the three flags read and writes ``results/``, ``<video>_i
 ``--stream_keep`` writes those three too, from the device bytes, for the frames that are swapped (the staged route also aligns and parses the
 trailing frames that ``drop_last`` never swaps; the stream does not decode them).
 
-The mp4 + audio mux of stage 3 is not built (no video encoder in this build).
+``--write_video [PATH]`` (with ``--paste_back`` or ``--stream``) ends stage 3 in a playable file: every pasted frame is JPEG-encoded on the
+GPU (reface_amd/mjpeg.py: libjpeg's baseline arithmetic, byte for byte) and appended in frame order to a Motion-JPEG AVI, by default
+``<outdir>/<video>_swapped.avi`` at ``--video_fps`` 25.  There is no audio track: the frames arrive as PNGs, so there is nothing to demux.
+The reference's H.264 mp4 + audio mux of stage 3 is not built (no video encoder in this build).
 """
 import argparse
 import os
@@ -128,7 +131,17 @@ def build_parser():
                    "stay on the host writer")
     p.add_argument("--stream_keep", action="store_true", help="--stream: also write <video>cropped_face/, <video>mask_frames/ and model_outputs/ "
                    "of the swapped frames, from the device bytes, off the launch thread")
+    p.add_argument("--write_video", type=str, nargs="?", const="", default=None, metavar="PATH", help="--paste_back / --stream: also JPEG-encode every "
+                   "pasted frame on the GPU (reface_amd/mjpeg.py) and write them in frame order as a Motion-JPEG AVI (default PATH: "
+                   "<outdir>/<video>_swapped.avi); no audio track")
+    p.add_argument("--video_fps", type=float, default=25.0, help="--write_video: frames per second of the file.  The reference reads the rate from "
+                   "the mp4 through cv2; here the frames arrive as PNGs and there is no container to read it from, so it is given (default 25)")
+    p.add_argument("--video_quality", type=int, default=90, help="--write_video: libjpeg quality, 1 .. 100 (default 90)")
+    p.add_argument("--video_subsampling", type=str, choices=["420", "444"], default="420", help="--write_video: chroma subsampling (default 420)")
     return p
+
+
+VIDEO_OPTIONS = ("write_video", "video_fps", "video_quality", "video_subsampling")
 
 
 def prepared_paths(opt):
@@ -270,6 +283,7 @@ def run_stream(opt):
     if opt.fixed_code:
         start_code = torch.randn([opt.C, opt.H // opt.f, opt.W // opt.f], device=device).unsqueeze(0).repeat(opt.n_samples, 1, 1, 1)
     writer = None if opt.skip_save else PngWriter(png_encoder=make_png_encoder(opt, device))
+    video = make_video(opt, device)
     n_done = 0
     held = []          # --gpu_png: the previous batch's enqueued encodes, handed to the writer only after this batch has been enqueued
     with torch.no_grad(), model.ema_scope():
@@ -287,6 +301,8 @@ def run_stream(opt):
             n_done += B
             if writer is None:
                 continue
+            if video is not None:          # (holds one batch back itself, as hand_over does for the PNG encodes)
+                video.push(pasted)
             if opt.gpu_png:
                 held = hand_over(writer, held, [([os.path.join(results, ids[i] + ".png") for i in idx], job) for idx, job in writer.encode_device(pasted)])
             else:
@@ -301,6 +317,7 @@ def run_stream(opt):
         hand_over(writer, held, [])
     torch.cuda.synchronize()
     n_files = writer.close() if writer is not None else 0
+    video_files = video.close() if video is not None else None
     n_pasted = n_files // 4 if keep else n_files
     if decoder is not None:
         from reface_amd.pngdec import counts_line
@@ -311,7 +328,7 @@ def run_stream(opt):
           f"transforms of all {len(paths)} frames to {sp['inv_transforms']}; "
           + (f"crops, label maps and swapped crops of the swapped frames kept in {', '.join(keep.values())}" if keep else
              "no crops, label maps or model_outputs files were written (--stream_keep writes them)")
-          + " (the mp4 + audio mux of the reference's stage 3 is not built).")
+          + (video_clause(opt, video_files) if video is not None else " (the mp4 + audio mux of the reference's stage 3 is not built)."))
     return n_done
 
 
@@ -331,6 +348,22 @@ def make_png_encoder(opt, device):
     return PngEncoder(device)
 
 
+def make_video(opt, device):
+    """--write_video: the device JPEG encoder, ordered sink and AVI writer the pasted frames also go through (None: no video)."""
+    if opt.write_video is None or opt.skip_save:
+        return None
+    from reface_amd.mjpeg import VideoOutput
+    path = opt.write_video or os.path.join(opt.outdir, os.path.basename(opt.target_video).split(".")[0] + "_swapped.avi")
+    return VideoOutput(path, opt.video_fps, opt.video_quality, opt.video_subsampling, device)
+
+
+def video_clause(opt, files):
+    """The closing line's account of the video: the files, their frame counts and what kind of file they are."""
+    names = ", ".join(f"{p} ({n} frames)" for p, n in files) or "no file (no frame was pasted)"
+    return (f"; video of {sum(n for _, n in files)} frames written to {names}: Motion-JPEG AVI, {opt.video_fps:g} fps, quality {opt.video_quality}, "
+            f"{opt.video_subsampling[0]}:{opt.video_subsampling[1]}:{opt.video_subsampling[2]}, no audio track.")
+
+
 def hand_over(writer, held, jobs):
     """The encodes enqueued one batch ago go to the writer threads now that the next batch is behind them in the stream; returns what to hold."""
     for paths, job in held:
@@ -340,7 +373,7 @@ def hand_over(writer, held, jobs):
 
 def main(argv=None):
     opt = build_parser().parse_args(argv)
-    print(opt)
+    print(argparse.Namespace(**{k: v for k, v in vars(opt).items() if k not in VIDEO_OPTIONS}))          # (the closing line states the video's settings)
     if opt.gpu_png and not (opt.paste_back or opt.stream or opt.stream_keep):
         raise SystemExit("inference_swap_video: --gpu_png encodes the pasted frames of results/ and needs --paste_back or --stream "
                          "(model_outputs/ stays on the host writer)")
@@ -349,6 +382,16 @@ def main(argv=None):
                          "is read (the crops of target_frames/ go through the dataset's host transforms)")
     if opt.gpu_png and opt.skip_save:
         print("inference_swap_video: --skip_save writes no files, so --gpu_png has nothing to encode")
+    if opt.write_video is not None:
+        if not (opt.paste_back or opt.stream or opt.stream_keep):
+            raise SystemExit("inference_swap_video: --write_video encodes the pasted frames of results/ into a video and needs --paste_back or --stream "
+                             "(model_outputs/ holds crops, not frames)")
+        if not 1 <= opt.video_quality <= 100:
+            raise SystemExit(f"inference_swap_video: --video_quality is libjpeg's 1 .. 100, got {opt.video_quality}")
+        if not opt.video_fps > 0:
+            raise SystemExit(f"inference_swap_video: --video_fps must be positive, got {opt.video_fps}")
+        if opt.skip_save:
+            print("inference_swap_video: --skip_save writes no files, so --write_video has nothing to encode")
     if opt.stream or opt.stream_keep:
         opt.stream = True
         return run_stream(opt)
@@ -402,6 +445,7 @@ def main(argv=None):
         from reface_amd.pasteback import PasteBack, PngWriter
         sp = pasteback_paths(opt)
         paster, writer = PasteBack(sp["video_frames"], sp["inv_transforms"]), PngWriter(png_encoder=make_png_encoder(opt, device))
+    video = make_video(opt, device) if paster is not None else None
     decoder = make_png_decoder(opt, device) if paster is not None else None
     held = []
     with torch.no_grad(), model.ema_scope():
@@ -420,8 +464,11 @@ def main(argv=None):
                 Image.fromarray(O.to_u8_hwc(res[i])).resize((1024, 1024), Image.BILINEAR).save(os.path.join(model_out, sid + ".png"))
             if paster is not None and decoder is not None and not opt.gpu_png:          # frames decoded and pasted on the device, encoded on the host
                 from reface_amd.pasteback import load_frames_device
-                for sid, frame in zip(ids, paster.paste_device(x_img, ids, load_frames_device(decoder, sp["video_frames"], ids))):
+                pasted = paster.paste_device(x_img, ids, load_frames_device(decoder, sp["video_frames"], ids))
+                for sid, frame in zip(ids, pasted):
                     writer.submit(os.path.join(opt.outdir, "results", sid + ".png"), frame.cpu().numpy())
+                if video is not None:
+                    video.push(pasted)
             elif paster is not None and opt.gpu_png:          # the pasted frames stay on the device and are encoded there
                 if decoder is not None:
                     from reface_amd.pasteback import load_frames_device
@@ -431,20 +478,26 @@ def main(argv=None):
                 pasted = paster.paste_device(x_img, ids, dev_frames)
                 held = hand_over(writer, held, [([os.path.join(opt.outdir, "results", ids[i] + ".png") for i in idx], job)
                                                 for idx, job in writer.encode_device(pasted)])
+                if video is not None:
+                    video.push(pasted)
             elif paster is not None:          # stage 3 (:705-724): the crops enlarged and warped into their frames on the device, PNGs encoded off this thread
-                for sid, frame in zip(ids, paster.paste(x_img, ids, frames)):
+                pasted = paster.paste(x_img, ids, frames)
+                for sid, frame in zip(ids, pasted):
                     writer.submit(os.path.join(opt.outdir, "results", sid + ".png"), frame)
+                if video is not None:          # the host-pasted frames go up once more, for the encoder
+                    video.push([torch.from_numpy(f).to(device) for f in pasted])
     if writer is not None:
         hand_over(writer, held, [])
     torch.cuda.synchronize()
     if paster is not None:
         paster.close()
         n_pasted = writer.close()
+        video_files = video.close() if video is not None else None
         if decoder is not None:
             from reface_amd.pngdec import counts_line
             print("inference_swap_video --" + counts_line(decoder, "frames"))
-        print(f"Swapped crops of {n_done} frames are in {model_out}; {n_pasted} pasted frames are in {os.path.join(opt.outdir, 'results')} "
-              f"(the mp4 + audio mux of the reference's stage 3 is not built).")
+        print(f"Swapped crops of {n_done} frames are in {model_out}; {n_pasted} pasted frames are in {os.path.join(opt.outdir, 'results')}"
+              + (video_clause(opt, video_files) if video is not None else " (the mp4 + audio mux of the reference's stage 3 is not built)."))
     else:
         print(f"Swapped crops of {n_done} frames are in {model_out}; the reference's stage 3 (paste back with the inverse alignment of every frame, "
               f"mp4 + audio) takes them from there (--paste_back pastes them back on the GPU).")
