@@ -37,6 +37,9 @@ def build_parser():
     p.add_argument("--recon_ckpt", type=str, default=DEFAULT_RECON_CKPT, help="(addition) net_recon weights (epoch_latest.pth); 'none' = the seeded weights the tests use")
     p.add_argument("--gpu_png_decode", action="store_true",
                    help="(addition) decode PNG files on the GPU (reface_amd/pngdec.py): the loader's workers only read bytes; the values are the same")
+    p.add_argument("--gpu_jpeg_decode", action="store_true",
+                   help="(addition) decode baseline JPEG files on the GPU (reface_amd/jpegdec.py): the loader's workers only read bytes; the values are "
+                        "the same.  Independent of --gpu_png_decode; both may be given")
     p.add_argument("--json", type=str, default=None,
                    help="(addition) write Expression_value, distances, labels, expression coefficients, image count and images/s (decode to score; engine "
                         "construction excluded) to this file")
@@ -64,7 +67,10 @@ def main(argv=None):
     state = load_recon_state(args.recon_ckpt)
     print("loading the model from %s" % args.recon_ckpt)
     scorer = ExprScorer(state, batch=args.batch_size, device=device)
-    if args.gpu_png_decode:
+    if args.gpu_jpeg_decode:          # one decoder behind both flags: every file goes by its signature
+        from reface_amd.jpegdec import FileDecoder
+        scorer.png_decoder = FileDecoder(device, png=args.gpu_png_decode, jpeg=True)
+    elif args.gpu_png_decode:
         from reface_amd.pngdec import PngDecoder
         scorer.png_decoder = PngDecoder(device)
     r = scorer.score_folders(args.path, num_workers=num_workers)
@@ -78,7 +84,10 @@ def main(argv=None):
             json.dump({"expression_value": r["expression_value"], "distances": [float(d) for d in r["distances"]], "labels": r["labels"],
                        "target_labels": r["target_labels"], "exp_target": r["exp_target"].tolist(), "exp_result": r["exp_result"].tolist(),
                        "images": r["images"], "images_per_s": r["images_per_s"], "seconds": r["seconds"]}, f)
-    if args.gpu_png_decode:          # (stderr: the printed lines stay what they are without the flag)
+    if args.gpu_jpeg_decode:          # (stderr: the printed lines stay what they are without the flags)
+        for line in scorer.png_decoder.lines():
+            print(line, file=sys.stderr)
+    elif args.gpu_png_decode:
         from reface_amd.pngdec import counts_line
         print(counts_line(scorer.png_decoder), file=sys.stderr)
     return r

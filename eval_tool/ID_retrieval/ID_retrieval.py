@@ -44,6 +44,9 @@ def build_parser():
                    help="(addition) ArcFace IR-SE50 weights; 'none' = the seeded weights the tests use")
     p.add_argument("--gpu_png_decode", action="store_true",
                    help="(addition) decode PNG files on the GPU (reface_amd/pngdec.py): the loader's workers only read bytes; the values are the same")
+    p.add_argument("--gpu_jpeg_decode", action="store_true",
+                   help="(addition) decode baseline JPEG files on the GPU (reface_amd/jpegdec.py): the loader's workers only read bytes; the values are "
+                        "the same.  Independent of --gpu_png_decode; both may be given")
     p.add_argument("--json", type=str, default=None,
                    help="(addition) write top1, top5, mean, similarities, labels, image count and images/s (decode to scores; engine construction excluded) to this file")
     p.add_argument("--precision", type=str, choices=["full", "bf16"], default="full", help="(addition) precision of the ArcFace engine")
@@ -65,7 +68,10 @@ def main(argv=None):
             raise RuntimeError("Invalid path: %s" % p)
     print("Loading ResNet ArcFace")
     scorer = IDScorer(load_arcface_state(args.arcface_ckpt), precision=args.precision, batch=args.batch_size, device=device)
-    if args.gpu_png_decode:
+    if args.gpu_jpeg_decode:          # one decoder behind both flags: every file goes by its signature
+        from reface_amd.jpegdec import FileDecoder
+        scorer.png_decoder = FileDecoder(device, png=args.gpu_png_decode, jpeg=True)
+    elif args.gpu_png_decode:
         from reface_amd.pngdec import PngDecoder
         scorer.png_decoder = PngDecoder(device)
     r = scorer.score_folders(args.path, dataset=args.dataset, num_workers=num_workers)
@@ -81,7 +87,10 @@ def main(argv=None):
             json.dump({"top1": r["top1"], "top5": r["top5"], "mean": r["mean"], "similarities": [float(s) for s in r["similarities"]],
                        "labels": r["labels"], "rank": [int(k) for k in r["rank"]], "pred": [int(k) for k in r["pred"]], "images": r["images"],
                        "images_per_s": r["images_per_s"], "seconds": r["seconds"], "precision": args.precision, "dataset": args.dataset}, f)
-    if args.gpu_png_decode:          # (stderr: the printed lines stay what they are without the flag)
+    if args.gpu_jpeg_decode:          # (stderr: the printed lines stay what they are without the flags)
+        for line in scorer.png_decoder.lines():
+            print(line, file=sys.stderr)
+    elif args.gpu_png_decode:
         from reface_amd.pngdec import counts_line
         print(counts_line(scorer.png_decoder), file=sys.stderr)
     return r

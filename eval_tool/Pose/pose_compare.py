@@ -34,6 +34,9 @@ def build_parser():
     p.add_argument("--hopenet_ckpt", type=str, default=DEFAULT_HOPENET_CKPT, help="(addition) Hopenet weights; 'none' = the seeded weights the tests use")
     p.add_argument("--gpu_png_decode", action="store_true",
                    help="(addition) decode PNG files on the GPU (reface_amd/pngdec.py): the loader's workers only read bytes; the values are the same")
+    p.add_argument("--gpu_jpeg_decode", action="store_true",
+                   help="(addition) decode baseline JPEG files on the GPU (reface_amd/jpegdec.py): the loader's workers only read bytes; the values are "
+                        "the same.  Independent of --gpu_png_decode; both may be given")
     p.add_argument("--json", type=str, default=None,
                    help="(addition) write Pose_value, distances, labels, degrees, image count and images/s (decode to score; engine construction excluded) to this file")
     return p
@@ -54,7 +57,10 @@ def main(argv=None):
             raise SystemExit(f"pose_compare: {p}: .npz statistics are not supported (the reference's .npz branch cannot run)")
     print("Loading hopenet")
     scorer = PoseScorer(load_hopenet_state(args.hopenet_ckpt), batch=args.batch_size, device=device)
-    if args.gpu_png_decode:
+    if args.gpu_jpeg_decode:          # one decoder behind both flags: every file goes by its signature
+        from reface_amd.jpegdec import FileDecoder
+        scorer.png_decoder = FileDecoder(device, png=args.gpu_png_decode, jpeg=True)
+    elif args.gpu_png_decode:
         from reface_amd.pngdec import PngDecoder
         scorer.png_decoder = PngDecoder(device)
     r = scorer.score_folders(args.path, num_workers=num_workers)
@@ -64,7 +70,10 @@ def main(argv=None):
             json.dump({"pose_value": r["pose_value"], "distances": [float(d) for d in r["distances"]], "labels": r["labels"],
                        "degrees_target": r["degrees_target"].tolist(), "degrees_result": r["degrees_result"].tolist(), "images": r["images"],
                        "images_per_s": r["images_per_s"], "seconds": r["seconds"]}, f)
-    if args.gpu_png_decode:          # (stderr: the printed lines stay what they are without the flag)
+    if args.gpu_jpeg_decode:          # (stderr: the printed lines stay what they are without the flags)
+        for line in scorer.png_decoder.lines():
+            print(line, file=sys.stderr)
+    elif args.gpu_png_decode:
         from reface_amd.pngdec import counts_line
         print(counts_line(scorer.png_decoder), file=sys.stderr)
     return r

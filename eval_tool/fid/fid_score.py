@@ -38,6 +38,9 @@ def build_parser():
     p.add_argument("--precision", type=str, default="full", choices=["full", "bf16"], help="(addition) tower arithmetic: fp32, or bf16 operands")
     p.add_argument("--gpu_png_decode", action="store_true",
                    help="(addition) decode PNG files on the GPU (reface_amd/pngdec.py): the loader's workers only read bytes; the values are the same")
+    p.add_argument("--gpu_jpeg_decode", action="store_true",
+                   help="(addition) decode baseline JPEG files on the GPU (reface_amd/jpegdec.py): the loader's workers only read bytes; the values are "
+                        "the same.  Independent of --gpu_png_decode; both may be given")
     p.add_argument("--json", type=str, default=None,
                    help="(addition) write the value, its four terms, image counts, images/s (decode to value; engine construction excluded) and the "
                         "number of images prepared on the host to this file")
@@ -59,7 +62,10 @@ def main(argv=None):
             raise RuntimeError("Invalid path: %s" % p)
     state, _ = load_fid_clip_state(args.clip_ckpt)
     scorer = FidScorer(state, precision=args.precision, batch=args.batch_size, device=device)
-    if args.gpu_png_decode:
+    if args.gpu_jpeg_decode:          # one decoder behind both flags: every file goes by its signature
+        from reface_amd.jpegdec import FileDecoder
+        scorer.png_decoder = FileDecoder(device, png=args.gpu_png_decode, jpeg=True)
+    elif args.gpu_png_decode:
         from reface_amd.pngdec import PngDecoder
         scorer.png_decoder = PngDecoder(device)
     r = scorer.score_folders(args.path, num_workers=num_workers)
@@ -71,7 +77,10 @@ def main(argv=None):
         with open(args.json, "w") as f:
             json.dump({k: r[k] for k in ("fid", "mean_term", "trace1", "trace2", "trace_covmean", "images1", "images2", "images", "host_prepared",
                                          "images_per_s", "seconds")} | {"precision": args.precision}, f)
-    if args.gpu_png_decode:          # (stderr: the printed lines stay what they are without the flag)
+    if args.gpu_jpeg_decode:          # (stderr: the printed lines stay what they are without the flags)
+        for line in scorer.png_decoder.lines():
+            print(line, file=sys.stderr)
+    elif args.gpu_png_decode:
         from reface_amd.pngdec import counts_line
         print(counts_line(scorer.png_decoder), file=sys.stderr)
     return r

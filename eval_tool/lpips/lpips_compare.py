@@ -36,6 +36,9 @@ def build_parser():
     p.add_argument("--print_sim", type=bool, default=False, help="also print one distance per result (any non-empty string is true)")
     p.add_argument("--gpu_png_decode", action="store_true",
                    help="(addition) decode PNG files on the GPU (reface_amd/pngdec.py): the loader's workers only read bytes; the values are the same")
+    p.add_argument("--gpu_jpeg_decode", action="store_true",
+                   help="(addition) decode baseline JPEG files on the GPU (reface_amd/jpegdec.py): the loader's workers only read bytes; the values are "
+                        "the same.  Independent of --gpu_png_decode; both may be given")
     p.add_argument("--json", type=str, default=None,
                    help="write LPIPS_value, distances, labels, image count and images/s (decode to score; engine construction excluded) to this file")
     return p
@@ -63,7 +66,10 @@ def main(argv=None):
     state = load_lpips_state(args.lpips_ckpt, args.net)
     print("Loading LPIPS(%s) from %s" % (args.net, args.lpips_ckpt))
     scorer = LPIPSScorer(state, net=args.net, batch=args.batch_size, device=device)
-    if args.gpu_png_decode:
+    if args.gpu_jpeg_decode:          # one decoder behind both flags: every file goes by its signature
+        from reface_amd.jpegdec import FileDecoder
+        scorer.png_decoder = FileDecoder(device, png=args.gpu_png_decode, jpeg=True)
+    elif args.gpu_png_decode:
         from reface_amd.pngdec import PngDecoder
         scorer.png_decoder = PngDecoder(device)
     try:
@@ -79,7 +85,10 @@ def main(argv=None):
         with open(args.json, "w") as f:
             json.dump({"lpips_value": r["lpips_value"], "distances": [float(d) for d in r["distances"]],
                        "labels": r["labels"], "net": args.net, "images": r["images"], "images_per_s": r["images_per_s"], "seconds": r["seconds"]}, f)
-    if args.gpu_png_decode:          # (stderr: the printed lines stay what they are without the flag)
+    if args.gpu_jpeg_decode:          # (stderr: the printed lines stay what they are without the flags)
+        for line in scorer.png_decoder.lines():
+            print(line, file=sys.stderr)
+    elif args.gpu_png_decode:
         from reface_amd.pngdec import counts_line
         print(counts_line(scorer.png_decoder), file=sys.stderr)
     return r

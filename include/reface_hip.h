@@ -710,6 +710,49 @@ int rf_jpeg_entropy(const int16_t* coef, int B, int mcu_rows, int mcus, int subs
 int rf_jpeg_pack(const void* slots_u8, int64_t slot_stride, const int* seg_bytes, int B, int mcu_rows, void* out_u8, int64_t out_stride, int* lengths,
                  void* stream);
 
+/*
+ * Baseline JPEG decoding on the device (the callers' --gpu_jpeg_decode and --video_in; reface_amd/jpegdec.py parses the markers, builds the
+ * tables, uploads the scans and raises the error codes).  8-bit sequential Huffman (SOF0), one interleaved scan, 1 component or 3 (YCbCr,
+ * luma sampled 1x1, 2x1 or 2x2 against chroma 1x1), H, W <= RF_JPEGDEC_MAX_SIDE.  A batch is described by RF_JPEGDEC_DESC int64 words per
+ * file, given twice: desc_host (read and range-checked by the entry point before anything is launched) and desc (the same words in device
+ * memory, read by the kernels):
+ *   0 scan_off, 1 scan_len   the entropy-coded bytes behind the SOS header up to EOI, at comp + scan_off
+ *   2 H, 3 W, 4 ncomp        ncomp = 1 | 3
+ *   5 hs, 6 vs               the luma sampling factors (1 | 2; 1 x 2 is not taken); chroma is 1 x 1
+ *   7 ri                     MCUs per restart interval, 0 = no DRI
+ *   8 coef_off               the file's first block in coef; its blocks follow in scan order (per MCU: hs * vs luma blocks, Cb, Cr)
+ *   9 plane_off              its component planes at planes + plane_off (a multiple of 16): Y, Cb, Cr, each padded to whole MCUs
+ *   10 out_c                 channels written: 3, or 1 for a 1-component file (which is replicated when out_c = 3)
+ *   11 pix_off, 12 row_stride   the image's pixels at pix + pix_off, row y at + y * row_stride bytes
+ *   13 tab_off               its tables at comp + tab_off (a multiple of 16), RF_JPEGDEC_TABLE_BYTES: 4 quantisation tables of 64 uint16
+ *                            in natural order, then 4 DC and 4 AC Huffman tables of 912 bytes (csrc/jpeg_decode.h: HuffTab); files may share
+ *   14 ivl_begin, 15 ivl_count   its intervals: ivl[ivl_begin ...]
+ *   16 tq, 17 td, 18 ta      the quantisation / DC / AC table number (0 .. 3) of component c in bits 8 c .. 8 c + 7
+ * status is int32 [B, 2]: the error code (0 = none; the codes of csrc/jpeg_decode.h) and the plan (0: one lane decodes the whole scan,
+ * 1: one lane per restart interval).
+ *   rf_jpeg_entropy_decode  : scans -> coef int16 [coef_blocks, 64], natural (de-zigzagged) order, zero-filled here.  ivl is int32
+ *                             [2, nivl] (the file of each interval, ascending; then the offset of its first byte in the file's scan: 0 for
+ *                             the first, 2 behind every FF D0..D7 for the others; ivl_host = the same words on the host).  One lane per
+ *                             interval, DC predictors 0 at its start; `lanes` (1 .. 64) lanes of every wave are used.  A file must hold
+ *                             ceil(MCUs / ri) intervals and the marker in front of interval k must be RST((k - 1) mod 8); every read is
+ *                             bounded by the interval's end, every write by its block range, every loop by blocks * 64 iterations; an
+ *                             invalid code, a coefficient index past 63 and running out of data are error codes.  A lane that meets an
+ *                             error stops and leaves its code (the first one of a file stays); the others are unaffected.  Writes status.
+ *   rf_jpeg_idct_u8         : coef -> planes u8: dequantisation and libjpeg's jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2; the result
+ *                             + 128 clamped to 0 .. 255, which equals libjpeg's masked range-limit table for any file made from pixels).
+ *   rf_jpeg_upsample_rgb_u8 : planes -> pixels: libjpeg's fancy (triangle) h2v1 / h2v2 chroma upsampling with the edges of the real
+ *                             downsampled plane, and its 16-bit-table YCbCr -> RGB.  Files whose error code is set are skipped by both.
+ */
+#define RF_JPEGDEC_DESC 24
+#define RF_JPEGDEC_TABLE_BYTES (512 + 8 * 912)
+#define RF_JPEGDEC_MAX_SIDE 8192
+int rf_jpeg_entropy_decode(const void* comp_u8, int64_t comp_bytes, const int64_t* desc_host, const int64_t* desc, int B, const int* ivl_host,
+                           const int* ivl, int nivl, int lanes, int16_t* coef, int64_t coef_blocks, int* status, void* stream);
+int rf_jpeg_idct_u8(const int16_t* coef, int64_t coef_blocks, const void* comp_u8, int64_t comp_bytes, const int64_t* desc_host, const int64_t* desc,
+                    int B, void* planes_u8, int64_t plane_bytes, const int* status, void* stream);
+int rf_jpeg_upsample_rgb_u8(const void* planes_u8, int64_t plane_bytes, const int64_t* desc_host, const int64_t* desc, int B, void* pix_u8,
+                            int64_t pix_bytes, const int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libreface_hip.so")
-SOURCES = ["gemm.hip", "gemm_f16.hip", "norm.hip", "attention.hip", "elementwise.hip", "encoder.hip", "ffn.hip", "smallconv.hip", "attnin.hip", "parsing.hip", "pasteback.hip", "align.hip", "video_prep.hip", "idscore.hip", "pose.hip", "expr.hip", "fid.hip", "lpips.hip", "pngenc.hip", "pngdec.hip", "jpegenc.hip"]
+SOURCES = ["gemm.hip", "gemm_f16.hip", "norm.hip", "attention.hip", "elementwise.hip", "encoder.hip", "ffn.hip", "smallconv.hip", "attnin.hip", "parsing.hip", "pasteback.hip", "align.hip", "video_prep.hip", "idscore.hip", "pose.hip", "expr.hip", "fid.hip", "lpips.hip", "pngenc.hip", "pngdec.hip", "jpegenc.hip", "jpegdec.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
 # per-file extras.  attention: keep MFMA accumulators in VGPRs -- the online softmax reads every score and rescales O each
 # tile, and with AGPR accumulators hipcc emitted ~160 v_accvgpr_read/write per KV tile (40 % of the loop's VALU work).
@@ -28,7 +28,9 @@ UNIT_DEPS = {"gemm_f16.hip": [os.path.join(CSRC, "gemm.hip")], "pasteback.hip": 
              "idscore.hip": [os.path.join(CSRC, "cv_u8.h")], "expr.hip": [os.path.join(CSRC, "pil_u8.h")],
              "fid.hip": [os.path.join(CSRC, "pil_u8.h")],
              # png_inflate.h: the zlib decoder core, compiled by hipcc here and by a host compiler into tests/pngdec_host_main.cpp
-             "pngdec.hip": [os.path.join(CSRC, "png_inflate.h")]}
+             "pngdec.hip": [os.path.join(CSRC, "png_inflate.h")],
+             # jpeg_decode.h: the JPEG entropy-decoder core, compiled by hipcc here and by a host compiler into tests/jpegdec_host_main.cpp
+             "jpegdec.hip": [os.path.join(CSRC, "jpeg_decode.h")]}
 
 
 

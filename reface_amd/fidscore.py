@@ -327,22 +327,26 @@ class _FidFolder(torch.utils.data.Dataset):
     everywhere (alpha dropped) -- for these the bytes PIL resizes in the image's own mode and then converts are the bytes of the RGB image
     resized -- and ("host", fp32 [3, 224, 224] from ``prep_host``) for every other mode or alpha."""
 
-    def __init__(self, files, gpu_png=False):
-        self.files, self.gpu_png = files, gpu_png
+    def __init__(self, files, kinds=()):
+        self.files, self.kinds = files, tuple(kinds)
 
     def __len__(self):
         return len(self.files)
 
     def __getitem__(self, i):
         from PIL import Image
-        if self.gpu_png:
+        if self.kinds:
             # --gpu_png_decode: RGB and grey PNG files travel as bytes, ("png", bytes), and are decoded on the device as
-            # .convert("RGB") -- the "u8" cases above that need no look at the pixels; RGBA (alpha must be inspected) stays here
+            # .convert("RGB") -- the "u8" cases above that need no look at the pixels; RGBA (alpha must be inspected) stays here.
+            # --gpu_jpeg_decode: likewise the JPEG files the device takes (grey or YCbCr: PIL's modes L and RGB)
             from . import pngdec
             with open(self.files[i], "rb") as f:
                 data = f.read()
-            info = pngdec.parse_png(data)
-            if info.route == "gpu" and info.bpp in (1, 3):
+            if "png" in self.kinds and data[:8] == pngdec.PNG_SIG:
+                info = pngdec.parse_png(data)
+                if info.route == "gpu" and info.bpp in (1, 3):
+                    return "png", data
+            elif pngdec.device_file(data, "RGB", tuple(k for k in self.kinds if k != "png")):
                 return "png", data
         return decode_item(Image.open(self.files[i]))
 
@@ -413,7 +417,10 @@ class FidScorer:
                 j = i + 1
                 while j < B and images_u8[j].shape == images_u8[i].shape:
                     j += 1
-                groups.append((torch.stack([torch.as_tensor(images_u8[k]) for k in range(i, j)]), i))
+                run = [torch.as_tensor(images_u8[k]) for k in range(i, j)]
+                if any(t.is_cuda for t in run):          # a run of device-decoded and host-decoded images of one size: the host ones go up first
+                    run = [t.to(self.dev) for t in run]
+                groups.append((torch.stack(run), i))
                 i = j
         for img, i in groups:
             if not (img.is_cuda and img.dim() == 4 and img.stride(3) == 1 and img.stride(2) == 3 and img.stride(1) == img.shape[2] * 3):
@@ -469,7 +476,7 @@ class FidScorer:
         if not files:
             raise ValueError(f"no image files in {folder}")
         batch = effective_batch(self.batch, len(files))
-        loader = torch.utils.data.DataLoader(_FidFolder(files, self.png_decoder is not None), batch_size=batch, shuffle=False, drop_last=False,
+        loader = torch.utils.data.DataLoader(_FidFolder(files, () if self.png_decoder is None else getattr(self.png_decoder, "kinds", ("png",))), batch_size=batch, shuffle=False, drop_last=False,
                                              num_workers=num_workers, collate_fn=_list_collate)
         feat = torch.empty((len(files), self.dim), dtype=F32, device=self.dev)
         at = host = 0

@@ -140,9 +140,9 @@ class _PairBytes(torch.utils.data.Dataset):
     """``_PairFolder`` for --gpu_png_decode: (image item, label-map item) as ``pngdec.ByteFolder`` gives them (file bytes where the device
     decodes the file, PIL's array where it does not)."""
 
-    def __init__(self, files, maskfiles):
+    def __init__(self, files, maskfiles, kinds=("png",)):
         from . import pngdec
-        self.img, self.lab = pngdec.ByteFolder(files, "RGB"), pngdec.ByteFolder(maskfiles[:len(files)], "L")
+        self.img, self.lab = pngdec.ByteFolder(files, "RGB", kinds), pngdec.ByteFolder(maskfiles[:len(files)], "L", kinds)
 
     def __len__(self):
         return len(self.img)
@@ -253,7 +253,7 @@ class IDScorer:
             if len(maskfiles) < len(files):
                 raise ValueError(f"{len(files)} images but only {len(maskfiles)} label maps")
             dec = self.png_decoder
-            pairs = torch.utils.data.DataLoader(_PairBytes(files, maskfiles), batch_size=batch, shuffle=False, drop_last=False, num_workers=num_workers,
+            pairs = torch.utils.data.DataLoader(_PairBytes(files, maskfiles, getattr(dec, "kinds", ("png",))), batch_size=batch, shuffle=False, drop_last=False, num_workers=num_workers,
                                                 collate_fn=pngdec.list_collate)
             loader = ((dec.decode([a for a, _ in items], "RGB"), [m[:, :, 0] for m in dec.decode([b for _, b in items], "L")]) for items in pairs)
         else:

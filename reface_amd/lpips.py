@@ -446,7 +446,7 @@ class LPIPSScorer:
         folder = None
         if dec is not None:
             from . import pngdec
-            folder = lambda files: pngdec.ByteFolder(files, "RGB")          # noqa: E731
+            folder = lambda files: pngdec.ByteFolder(files, "RGB", getattr(dec, "kinds", ("png",)))          # noqa: E731
         loader = torch.utils.data.DataLoader(_PairFolder(targets, results, labels, folder), batch_sampler=[list(range(a, b)) for a, b in chunks],
                                              num_workers=num_workers, collate_fn=_pairs_collate)
         with torch.no_grad():

@@ -10,7 +10,8 @@ is byte for byte the one libjpeg(-turbo) writes for ``quality``, ``subsampling``
 ``JpegEncoder.encode_async`` enqueues the three kernels on the current stream, records an event and returns; ``JpegJob.result()`` -- meant
 for a writer thread -- waits for the event and copies lengths and bytes through pinned memory on the encoder's copy stream.  ``AviWriter`` is
 a plain RIFF writer (``hdrl`` / ``movi`` / ``idx1``), ``VideoSink`` the one thread that appends jobs' frames in submission order, and
-``VideoOutput`` the three together as the CLI uses them.  There is no audio track.
+``VideoOutput`` the three together as the CLI uses them.  There is no audio track.  ``AviReader`` is the way back: the frames of a
+Motion-JPEG AVI file as bytes, for reface_amd/jpegdec.py to decode (``--video_in``).
 """
 import os
 import queue
@@ -357,6 +358,159 @@ class AviWriter:
         if self.f is not None:
             self._finish()
         return list(self.files)
+
+
+class AviReader:
+    """The frames of a Motion-JPEG RIFF ``AVI `` file, as ``AviWriter`` (or any other muxer) writes them: ``width``, ``height``, ``fps`` (=
+    ``rate`` / ``scale`` of the video stream header), ``len()``, ``frame(i) -> bytes`` and iteration.  The frames are the ``00dc`` / ``00db``
+    chunks of ``LIST movi`` in file order (``LIST rec `` groups are entered); ``idx1`` is only a cross-check.  ``AviWriter``'s continuation
+    parts (``<stem>.002.avi``, ...) are followed.  Every offset is checked against the file size; a malformed file raises ``ValueError``
+    naming the file and the offset, and so does any codec other than MJPG."""
+
+    def __init__(self, path):
+        self.path = str(path)
+        self.parts, self._open = [], {}
+        head = self._parse(self.path)
+        self.width, self.height, self.rate, self.scale = head["width"], head["height"], head["rate"], head["scale"]
+        self.fps = self.rate / self.scale
+        self.parts.append((self.path, head["frames"]))
+        stem, ext = os.path.splitext(self.path)
+        k = 2
+        while os.path.exists(f"{stem}.{k:03d}{ext or '.avi'}"):
+            part = f"{stem}.{k:03d}{ext or '.avi'}"
+            h = self._parse(part)
+            if (h["width"], h["height"], h["rate"], h["scale"]) != (self.width, self.height, self.rate, self.scale):
+                raise ValueError(f"{part}: at offset 0: its size or rate is not that of {self.path}")
+            self.parts.append((part, h["frames"]))
+            k += 1
+        self._starts = [0]
+        for _, frames in self.parts:
+            self._starts.append(self._starts[-1] + len(frames))
+
+    @staticmethod
+    def _parse(path):
+        size = os.path.getsize(path)
+
+        def bad(off, what):
+            return ValueError(f"{path}: at offset {off}: {what}")
+
+        with open(path, "rb") as f:
+            def header(off, end):
+                if off + 8 > end:
+                    raise bad(off, "truncated chunk header")
+                f.seek(off)
+                cc, n = struct.unpack("<4sI", f.read(8))
+                if off + 8 + n > end:
+                    raise bad(off, f"chunk {cc!r} of {n} bytes runs past its parent (which ends at {end})")
+                return cc, n
+
+            def body(off, n):
+                f.seek(off)
+                return f.read(n)
+
+            if size < 12:
+                raise bad(0, "not a RIFF AVI file")
+            riff, n, kind = struct.unpack("<4sI4s", body(0, 12))
+            if riff != b"RIFF" or kind != b"AVI ":
+                raise bad(0, "not a RIFF AVI file")
+            if 8 + n > size:
+                raise bad(4, f"the RIFF size {n} runs past the file's {size} bytes")
+            end = 8 + n
+            avih = strh = strf = movi = idx1 = None
+            off = 12
+            while off + 8 <= end:
+                cc, n = header(off, end)
+                if cc == b"LIST":
+                    if n < 4:
+                        raise bad(off, "LIST without a type")
+                    kind = body(off + 8, 4)
+                    if kind == b"hdrl":
+                        p, hend, in_strl = off + 12, off + 8 + n, None
+                        while p + 8 <= hend:
+                            c2, n2 = header(p, hend)
+                            if c2 == b"avih":
+                                if n2 < 56:
+                                    raise bad(p, "avih is shorter than 56 bytes")
+                                avih = struct.unpack("<14I", body(p + 8, 56))
+                            elif c2 == b"LIST" and n2 >= 4 and body(p + 8, 4) == b"strl":
+                                q, send, sh, sf = p + 12, p + 8 + n2, None, None
+                                while q + 8 <= send:
+                                    c3, n3 = header(q, send)
+                                    if c3 == b"strh":
+                                        if n3 < 48:
+                                            raise bad(q, "strh is shorter than 48 bytes")
+                                        sh = struct.unpack("<4s4sIHHIIIIIIII", body(q + 8, 48))
+                                    elif c3 == b"strf" and n3 >= 40:
+                                        sf = struct.unpack("<IiiHH4sIiiII", body(q + 8, 40))
+                                    q += 8 + n3 + (n3 & 1)
+                                if sh is not None and sh[0] == b"vids" and strh is None:
+                                    if sf is None:
+                                        raise bad(p, "the video stream has no strf")
+                                    strh, strf = sh, sf
+                            p += 8 + n2 + (n2 & 1)
+                    elif kind == b"movi" and movi is None:
+                        movi = (off + 8, off + 8 + n)          # the `movi` tag, the list's end
+                elif cc == b"idx1":
+                    idx1 = (off + 8, n)
+                off += 8 + n + (n & 1)
+            if avih is None or strh is None:
+                raise bad(12, "no avih or no video stream header")
+            if movi is None:
+                raise bad(12, "no LIST movi")
+            codec = strf[5]
+            if codec.upper() != b"MJPG" or strh[1].upper() not in (b"MJPG", b"\0\0\0\0"):
+                raise bad(12, f"the video stream's codec is {codec!r} (handler {strh[1]!r}), not MJPG: only Motion-JPEG AVI files are read")
+            if strh[6] == 0 or strh[7] == 0:
+                raise bad(12, "the video stream's rate or scale is 0")
+            frames, stack = [], [(movi[0] + 4, movi[1])]
+            while stack:
+                p, pend = stack.pop()
+                while p + 8 <= pend:
+                    cc, n = header(p, pend)
+                    if cc == b"LIST" and n >= 4 and body(p + 8, 4) == b"rec ":
+                        stack.append((p + 8 + n + (n & 1), pend))
+                        p, pend = p + 12, p + 8 + n
+                        continue
+                    if cc in (b"00dc", b"00db") and n > 0:
+                        frames.append((p + 8, n))
+                    p += 8 + n + (n & 1)
+            if idx1 is not None:
+                i0, n = idx1
+                ents = [struct.unpack_from("<4sIII", e) for e in (body(i0 + 16 * k, 16) for k in range(n // 16))]
+                ents = [e for e in ents if e[0] in (b"00dc", b"00db") and e[3] > 0]
+                if len(ents) != len(frames):
+                    raise bad(i0, f"idx1 lists {len(ents)} frames, LIST movi holds {len(frames)}")
+                base = movi[0] if not ents or ents[0][2] + movi[0] + 8 == frames[0][0] else 0          # offsets from the `movi` tag, or from the file start
+                for k, (e, fr) in enumerate(zip(ents, frames)):
+                    if (e[2] + base + 8, e[3]) != fr:
+                        raise bad(i0 + 16 * k, f"idx1 entry {k} does not point at frame {k}")
+        return {"width": int(strf[1]), "height": abs(int(strf[2])), "rate": strh[7], "scale": strh[6], "frames": frames, "total_frames": avih[4]}
+
+    def __len__(self):
+        return self._starts[-1]
+
+    def frame(self, i):
+        if not 0 <= i < len(self):
+            raise IndexError(f"{self.path}: frame {i} of {len(self)}")
+        k = max(j for j in range(len(self.parts)) if self._starts[j] <= i)
+        path, frames = self.parts[k]
+        f = self._open.get(k)
+        if f is None:
+            f = self._open[k] = open(path, "rb")
+        off, n = frames[i - self._starts[k]]
+        f.seek(off)
+        data = f.read(n)
+        if len(data) != n:
+            raise ValueError(f"{path}: at offset {off}: frame {i} is cut short")
+        return data
+
+    def __iter__(self):
+        return (self.frame(i) for i in range(len(self)))
+
+    def close(self):
+        for f in self._open.values():
+            f.close()
+        self._open = {}
 
 
 class VideoSink:

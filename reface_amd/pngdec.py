@@ -406,12 +406,13 @@ class PngDecoder:
 
 
 class ByteFolder(torch.utils.data.Dataset):
-    """The files of a folder for a loader whose consumer decodes on the device: an item is the file's bytes where ``PngDecoder.decode`` with
-    this ``mode`` takes the file on the device, and PIL's array (a host tensor [H, W, C], decoded here, in the worker) where it does not.
-    ``PngDecoder.decode_async`` accepts both kinds of item."""
+    """The files of a folder for a loader whose consumer decodes on the device: an item is the file's bytes where the decoder of the file's
+    kind (``kinds``: "png" for ``PngDecoder``, "jpeg" for ``jpegdec.JpegDecoder``; ``jpegdec.FileDecoder`` says which it holds) takes the
+    file on the device under this ``mode``, and PIL's array (a host tensor [H, W, C], decoded here, in the worker) where it does not.
+    The decoders' ``decode_async`` accepts both kinds of item."""
 
-    def __init__(self, files, mode=None):
-        self.files, self.mode = list(files), mode
+    def __init__(self, files, mode=None, kinds=("png",)):
+        self.files, self.mode, self.kinds = list(files), mode, tuple(kinds)
 
     def __len__(self):
         return len(self.files)
@@ -419,10 +420,20 @@ class ByteFolder(torch.utils.data.Dataset):
     def __getitem__(self, i):
         with open(self.files[i], "rb") as f:
             data = f.read()
-        info = parse_png(data)
-        if info.route == "gpu" and _out_channels(info.bpp, self.mode) is not None:
+        if device_file(data, self.mode, self.kinds):
             return data
         return _pil_decode(data, self.mode)
+
+
+def device_file(data, mode, kinds=("png",)):
+    """Whether the decoder of the file's kind (by signature), if it is among `kinds`, decodes these bytes on the device under `mode`."""
+    if "png" in kinds and data[:8] == PNG_SIG:
+        info = parse_png(data)
+        return info.route == "gpu" and _out_channels(info.bpp, mode) is not None
+    if "jpeg" in kinds and data[:2] == b"\xff\xd8":
+        from . import jpegdec
+        return jpegdec.route(data, mode)[0].route == "gpu"
+    return False
 
 
 def list_collate(items):
@@ -432,7 +443,7 @@ def list_collate(items):
 def device_batches(decoder, files, batch, num_workers, mode):
     """The files of a folder as device uint8 images, one list (or, when all of a batch came from the device at one shape, one stacked
     tensor [B, H, W, C]) per loader batch: the workers read bytes, this process decodes them on the device."""
-    loader = torch.utils.data.DataLoader(ByteFolder(files, mode), batch_size=batch, shuffle=False, drop_last=False, num_workers=num_workers,
+    loader = torch.utils.data.DataLoader(ByteFolder(files, mode, getattr(decoder, "kinds", ("png",))), batch_size=batch, shuffle=False, drop_last=False, num_workers=num_workers,
                                          collate_fn=list_collate)
     for items in loader:
         job = decoder.decode_async(items, mode)

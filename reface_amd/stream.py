@@ -40,6 +40,49 @@ class FrameDataset(Dataset):
         return torch.from_numpy(np.array(load_frame(self.frames_dir, i))), str(i).zfill(12)
 
 
+class AviFrameDataset(Dataset):
+    """The host half of the stream for --video_in: the JPEG bytes of frame i of a Motion-JPEG AVI file (``mjpeg.AviReader``, opened in the
+    process that reads), with the dataset's 12-digit id.  Collate with ``frame_items_collate``; ``VideoFrames`` decodes on the device."""
+
+    def __init__(self, path, n):
+        self.path, self.n, self._reader = str(path), int(n), None
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        if self._reader is None:
+            from .mjpeg import AviReader
+            self._reader = AviReader(self.path)
+        return self._reader.frame(i), str(i).zfill(12)
+
+    def __getstate__(self):          # (a worker opens its own file)
+        return {"path": self.path, "n": self.n, "_reader": None}
+
+
+class VideoFrames:
+    """The frames of a Motion-JPEG AVI file as uint8 RGB device tensors [H, W, 3] (what ``load_frame`` gives for the PNG of the same frame):
+    ``reader`` an ``mjpeg.AviReader``, ``decoder`` a ``jpegdec.JpegDecoder``.  ``frames[i]`` and ``batch(ids)`` decode on demand; a damaged
+    frame raises ``jpegdec.JpegDecodeError`` naming the file and the frame."""
+
+    def __init__(self, reader, decoder):
+        self.reader, self.decoder = reader, decoder
+
+    def __len__(self):
+        return len(self.reader)
+
+    def items(self, ids, datas=None):
+        """(name, bytes) of the frames `ids` for ``decoder.decode_async(..., "RGB")``; `datas`: their bytes when a loader has read them."""
+        datas = [self.reader.frame(int(i)) for i in ids] if datas is None else datas
+        return [(f"{self.reader.path}#{int(i)}", d) for i, d in zip(ids, datas)]
+
+    def batch(self, ids):
+        return self.decoder.decode(self.items(ids), "RGB")
+
+    def __getitem__(self, i):
+        return self.batch([i])[0]
+
+
 def frame_items_collate(items):
     return [f for f, _ in items], [i for _, i in items]
 

@@ -46,6 +46,11 @@ trailing frames that ``drop_last`` never swaps; the stream does not decode them)
 GPU (reface_amd/mjpeg.py: libjpeg's baseline arithmetic, byte for byte) and appended in frame order to a Motion-JPEG AVI, by default
 ``<outdir>/<video>_swapped.avi`` at ``--video_fps`` 25.  There is no audio track: the frames arrive as PNGs, so there is nothing to demux.
 The reference's H.264 mp4 + audio mux of stage 3 is not built (no video encoder in this build).
+
+``--video_in FILE.avi`` (with ``--paste_back`` or ``--stream``) takes the full frames from a Motion-JPEG AVI file -- the kind ``--write_video``
+writes -- instead of ``<Base_dir>/<video>/<i>.png``: frame i is the file's i-th frame, decoded on the GPU (reface_amd/jpegdec.py: exactly
+PIL's array) as RGB; ``--landmarks`` index its frames (and are required: dlib reads image files), ``drop_last`` and the ids are unchanged,
+and ``--write_video`` without ``--video_fps`` takes the input's rate.
 """
 import argparse
 import os
@@ -136,12 +141,39 @@ def build_parser():
                    "<outdir>/<video>_swapped.avi); no audio track")
     p.add_argument("--video_fps", type=float, default=25.0, help="--write_video: frames per second of the file.  The reference reads the rate from "
                    "the mp4 through cv2; here the frames arrive as PNGs and there is no container to read it from, so it is given (default 25)")
+    p.add_argument("--video_in", type=str, default=None, metavar="FILE.avi", help="--paste_back / --stream: frame i is the i-th frame of this "
+                   "Motion-JPEG AVI file (as --write_video writes them), decoded on the GPU (reface_amd/jpegdec.py) and used where "
+                   "<Base_dir>/<video>/<i>.png is used otherwise; --landmarks index its frames.  With --write_video and no --video_fps the output "
+                   "takes this file's rate")
     p.add_argument("--video_quality", type=int, default=90, help="--write_video: libjpeg quality, 1 .. 100 (default 90)")
     p.add_argument("--video_subsampling", type=str, choices=["420", "444"], default="420", help="--write_video: chroma subsampling (default 420)")
     return p
 
 
-VIDEO_OPTIONS = ("write_video", "video_fps", "video_quality", "video_subsampling")
+VIDEO_OPTIONS = ("write_video", "video_fps", "video_quality", "video_subsampling", "video_in")
+_READERS = {}
+
+
+def video_reader(opt):
+    """--video_in: the AviReader of the file, opened once per run (None without the flag).  Exits naming what is wrong with the file."""
+    if not opt.video_in:
+        return None
+    if opt.video_in not in _READERS:
+        from reface_amd.mjpeg import AviReader
+        try:
+            _READERS[opt.video_in] = AviReader(opt.video_in)
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"inference_swap_video: --video_in: {e}")
+    return _READERS[opt.video_in]
+
+
+def video_source(opt, device):
+    """--video_in: the file's frames as device tensors (reface_amd.stream.VideoFrames: AviReader + the device JPEG decoder), else None."""
+    if not opt.video_in:
+        return None
+    from reface_amd.jpegdec import JpegDecoder
+    from reface_amd.stream import VideoFrames
+    return VideoFrames(video_reader(opt), JpegDecoder(device))
 
 
 def prepared_paths(opt):
@@ -163,12 +195,16 @@ def check_pasteback_inputs(opt, pp):
     """Paths stage 3 needs that are missing: the frames directory and the .npy, then (when both exist) the frame of every crop that a
     drop_last run swaps and its row of inverse transforms."""
     sp = pasteback_paths(opt)
-    missing = [sp["video_frames"]] if not os.path.isdir(sp["video_frames"]) else []
+    reader = video_reader(opt)          # --video_in: the frames come from the file, not from <Base_dir>/<video>/
+    missing = [sp["video_frames"]] if reader is None and not os.path.isdir(sp["video_frames"]) else []
     missing += [sp["inv_transforms"]] if not os.path.isfile(sp["inv_transforms"]) else []
     if missing or not os.path.isdir(pp["frames"]):
         return missing
     n = len(os.listdir(pp["frames"])) // max(1, opt.n_samples) * max(1, opt.n_samples)
-    missing += [p for p in (os.path.join(sp["video_frames"], f"{i}.png") for i in range(n)) if not os.path.isfile(p)]
+    if reader is None:
+        missing += [p for p in (os.path.join(sp["video_frames"], f"{i}.png") for i in range(n)) if not os.path.isfile(p)]
+    elif len(reader) < n:
+        missing.append(f"{opt.video_in} (frames 0..{n - 1}: the file holds {len(reader)})")
     from reface_amd.pasteback import load_inv_transforms
     if len(load_inv_transforms(sp["inv_transforms"])) < n:
         missing.append(f"{sp['inv_transforms']} (rows for frames 0..{n - 1})")
@@ -181,11 +217,20 @@ def check_align_inputs(opt):
     from reface_amd import align as A
     frames_dir = pasteback_paths(opt)["video_frames"]
     problems = []
-    n = len([f for f in os.listdir(frames_dir) if f.endswith(".png")]) if os.path.isdir(frames_dir) else 0
-    if n == 0:
-        problems.append(f"{frames_dir} (the full frames <i>.png, i = 0 .. N-1)")
-    paths = [os.path.join(frames_dir, f"{i}.png") for i in range(n)]
-    problems += [p for p in paths if not os.path.isfile(p)]
+    reader = video_reader(opt)
+    if reader is not None:          # --video_in: frame i of the file stands where <frames_dir>/<i>.png stands
+        n = len(reader)
+        if n == 0:
+            problems.append(f"{opt.video_in} (it holds no frame)")
+        paths = [f"{opt.video_in}#{i}" for i in range(n)]
+        if not opt.landmarks:
+            problems.append("--landmarks (dlib reads image files; the frames of --video_in are not files)")
+    else:
+        n = len([f for f in os.listdir(frames_dir) if f.endswith(".png")]) if os.path.isdir(frames_dir) else 0
+        if n == 0:
+            problems.append(f"{frames_dir} (the full frames <i>.png, i = 0 .. N-1)")
+        paths = [os.path.join(frames_dir, f"{i}.png") for i in range(n)]
+        problems += [p for p in paths if not os.path.isfile(p)]
     if not os.path.isfile(opt.src_image):
         problems.append(f"{opt.src_image} (--src_image)")
     lm = src_lm = None
@@ -211,6 +256,8 @@ def run_align(opt, paths, lm, src_lm):
     os.makedirs(pp["frames"], exist_ok=True)
     os.makedirs(os.path.dirname(pp["src"]), exist_ok=True)
     align_to_disk([opt.src_image], src_lm, [pp["src"]])
+    if opt.video_in:          # the frames as device tensors, decoded when the aligner asks for them
+        paths = video_source(opt, torch.device("cuda"))
     inv = align_to_disk(paths, lm, [os.path.join(pp["frames"], f"{i}.png") for i in range(len(paths))], batch=max(1, opt.n_samples))
     np.save(pasteback_paths(opt)["inv_transforms"], inv)
     print(f"inference_swap_video: {len(paths)} frames aligned into {pp['frames']} ({int((~np.isfinite(lm).all(axis=(1, 2))).sum())} without a face "
@@ -275,10 +322,15 @@ def run_stream(opt):
         os.makedirs(d, exist_ok=True)
     ref1 = load_source_reference(pp["src"], pp["src_mask"], test_args["preserve_mask_src_FFHQ"]).to(device)
     ns = max(1, opt.n_samples)
-    ds = FrameDataset(sp["video_frames"], len(paths) // ns * ns, raw=opt.gpu_png_decode)          # drop_last: the trailing partial batch is never swapped, so never decoded
+    source = video_source(opt, device)
+    if source is not None:          # --video_in: the workers read the frames' JPEG bytes out of the AVI file
+        from reface_amd.stream import AviFrameDataset
+        ds = AviFrameDataset(opt.video_in, len(paths) // ns * ns)
+    else:
+        ds = FrameDataset(sp["video_frames"], len(paths) // ns * ns, raw=opt.gpu_png_decode)          # drop_last: the trailing partial batch is never swapped, so never decoded
     loader = torch.utils.data.DataLoader(ds, batch_size=ns, num_workers=opt.num_workers, pin_memory=True, shuffle=False, drop_last=True,
-                                         collate_fn=frame_items_collate if opt.gpu_png_decode else raw_collate)
-    decoder = make_png_decoder(opt, device)
+                                         collate_fn=frame_items_collate if opt.gpu_png_decode or source is not None else raw_collate)
+    decoder = source.decoder if source is not None else make_png_decoder(opt, device)
     start_code = None
     if opt.fixed_code:
         start_code = torch.randn([opt.C, opt.H // opt.f, opt.W // opt.f], device=device).unsqueeze(0).repeat(opt.n_samples, 1, 1, 1)
@@ -289,7 +341,7 @@ def run_stream(opt):
     with torch.no_grad(), model.ema_scope():
         for frames, ids in loader:          # (the iterator draws its base seed from the CPU generator, as the staged loader's does)
             if decoder is not None:          # the workers read bytes: the frames are decoded here, on the device
-                job = decoder.decode_async(frames)
+                job = decoder.decode_async(*((source.items(ids, frames), "RGB") if source is not None else (frames,)))
                 frames = job.result()
                 frames = job.batch if job.batch is not None else frames
             test_batch, kw, state = vs.prepare(frames, ids)
@@ -320,8 +372,7 @@ def run_stream(opt):
     video_files = video.close() if video is not None else None
     n_pasted = n_files // 4 if keep else n_files
     if decoder is not None:
-        from reface_amd.pngdec import counts_line
-        print("inference_swap_video --" + counts_line(decoder, "frames"))
+        print("inference_swap_video --" + decoder_line(opt, decoder))
     left = len(paths) - n_done
     print(f"inference_swap_video --stream: {n_done} of {len(paths)} frames swapped and pasted on the device"
           + (f" ({left} trailing frames are not swapped: drop_last)" if left else "") + f"; {n_pasted} pasted frames written to {results}, inverse "
@@ -338,6 +389,15 @@ def make_png_decoder(opt, device):
         return None
     from reface_amd.pngdec import PngDecoder
     return PngDecoder(device)
+
+
+def decoder_line(opt, decoder):
+    """The line that says where the frames were decoded (--gpu_png_decode's, or --video_in's)."""
+    if opt.video_in:
+        from reface_amd.jpegdec import counts_line
+    else:
+        from reface_amd.pngdec import counts_line
+    return counts_line(decoder, "frames")
 
 
 def make_png_encoder(opt, device):
@@ -382,6 +442,16 @@ def main(argv=None):
                          "is read (the crops of target_frames/ go through the dataset's host transforms)")
     if opt.gpu_png and opt.skip_save:
         print("inference_swap_video: --skip_save writes no files, so --gpu_png has nothing to encode")
+    if opt.video_in:
+        if not (opt.paste_back or opt.stream or opt.stream_keep):
+            raise SystemExit("inference_swap_video: --video_in supplies the video's full frames for --paste_back or --stream; without either no frame "
+                             "is read (the crops of target_frames/ go through the dataset's host transforms)")
+        if opt.gpu_png_decode:
+            raise SystemExit("inference_swap_video: the frames of --video_in are JPEG and are decoded on the GPU already; --gpu_png_decode has no PNG "
+                             "frame to decode")
+        reader = video_reader(opt)
+        if opt.write_video is not None and not any(a == "--video_fps" or a.startswith("--video_fps=") for a in (sys.argv[1:] if argv is None else argv)):
+            opt.video_fps = reader.fps          # the output takes the input's rate
     if opt.write_video is not None:
         if not (opt.paste_back or opt.stream or opt.stream_keep):
             raise SystemExit("inference_swap_video: --write_video encodes the pasted frames of results/ into a video and needs --paste_back or --stream "
@@ -446,7 +516,14 @@ def main(argv=None):
         sp = pasteback_paths(opt)
         paster, writer = PasteBack(sp["video_frames"], sp["inv_transforms"]), PngWriter(png_encoder=make_png_encoder(opt, device))
     video = make_video(opt, device) if paster is not None else None
-    decoder = make_png_decoder(opt, device) if paster is not None else None
+    source = video_source(opt, device) if paster is not None else None
+    decoder = (source.decoder if source is not None else make_png_decoder(opt, device)) if paster is not None else None
+
+    def device_frames(ids):
+        if source is not None:
+            return source.batch(ids)
+        from reface_amd.pasteback import load_frames_device
+        return load_frames_device(decoder, sp["video_frames"], ids)
     held = []
     with torch.no_grad(), model.ema_scope():
         for test_batch, prior, kw, ids in loader:
@@ -463,16 +540,14 @@ def main(argv=None):
             for i, sid in enumerate(ids):
                 Image.fromarray(O.to_u8_hwc(res[i])).resize((1024, 1024), Image.BILINEAR).save(os.path.join(model_out, sid + ".png"))
             if paster is not None and decoder is not None and not opt.gpu_png:          # frames decoded and pasted on the device, encoded on the host
-                from reface_amd.pasteback import load_frames_device
-                pasted = paster.paste_device(x_img, ids, load_frames_device(decoder, sp["video_frames"], ids))
+                pasted = paster.paste_device(x_img, ids, device_frames(ids))
                 for sid, frame in zip(ids, pasted):
                     writer.submit(os.path.join(opt.outdir, "results", sid + ".png"), frame.cpu().numpy())
                 if video is not None:
                     video.push(pasted)
             elif paster is not None and opt.gpu_png:          # the pasted frames stay on the device and are encoded there
                 if decoder is not None:
-                    from reface_amd.pasteback import load_frames_device
-                    dev_frames = load_frames_device(decoder, sp["video_frames"], ids)
+                    dev_frames = device_frames(ids)
                 else:
                     dev_frames = [torch.from_numpy(np.array(f.result(), copy=True)).to(device) for f in frames]
                 pasted = paster.paste_device(x_img, ids, dev_frames)
@@ -494,8 +569,7 @@ def main(argv=None):
         n_pasted = writer.close()
         video_files = video.close() if video is not None else None
         if decoder is not None:
-            from reface_amd.pngdec import counts_line
-            print("inference_swap_video --" + counts_line(decoder, "frames"))
+            print("inference_swap_video --" + decoder_line(opt, decoder))
         print(f"Swapped crops of {n_done} frames are in {model_out}; {n_pasted} pasted frames are in {os.path.join(opt.outdir, 'results')}"
               + (video_clause(opt, video_files) if video is not None else " (the mp4 + audio mux of the reference's stage 3 is not built)."))
     else:
