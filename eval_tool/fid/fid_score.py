@@ -41,6 +41,9 @@ def build_parser():
     p.add_argument("--gpu_jpeg_decode", action="store_true",
                    help="(addition) decode baseline JPEG files on the GPU (reface_amd/jpegdec.py): the loader's workers only read bytes; the values are "
                         "the same.  Independent of --gpu_png_decode; both may be given")
+    p.add_argument("--gpu_jpeg_parallel", action="store_true",
+                   help="(addition) with --gpu_jpeg_decode: files without restart markers are decoded by one lane per sub-sequence of the scan "
+                        "(the self-synchronising plan of reface_amd/jpegdec.py) instead of one lane per file; the values are the same")
     p.add_argument("--json", type=str, default=None,
                    help="(addition) write the value, its four terms, image counts, images/s (decode to value; engine construction excluded) and the "
                         "number of images prepared on the host to this file")
@@ -50,6 +53,9 @@ def build_parser():
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.gpu_jpeg_parallel and not args.gpu_jpeg_decode:
+        raise SystemExit("fid_score: --gpu_jpeg_parallel chooses a plan of the GPU JPEG decoder and needs --gpu_jpeg_decode; without it no file "
+                         "is decoded on the GPU")
     import numpy as np
     import torch
     from reface_amd.fidscore import FidScorer, load_fid_clip_state
@@ -64,7 +70,7 @@ def main(argv=None):
     scorer = FidScorer(state, precision=args.precision, batch=args.batch_size, device=device)
     if args.gpu_jpeg_decode:          # one decoder behind both flags: every file goes by its signature
         from reface_amd.jpegdec import FileDecoder
-        scorer.png_decoder = FileDecoder(device, png=args.gpu_png_decode, jpeg=True)
+        scorer.png_decoder = FileDecoder(device, png=args.gpu_png_decode, jpeg=True, jpeg_parallel=args.gpu_jpeg_parallel)
     elif args.gpu_png_decode:
         from reface_amd.pngdec import PngDecoder
         scorer.png_decoder = PngDecoder(device)

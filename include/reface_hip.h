@@ -728,8 +728,9 @@ int rf_jpeg_pack(const void* slots_u8, int64_t slot_stride, const int* seg_bytes
  *                            in natural order, then 4 DC and 4 AC Huffman tables of 912 bytes (csrc/jpeg_decode.h: HuffTab); files may share
  *   14 ivl_begin, 15 ivl_count   its intervals: ivl[ivl_begin ...]
  *   16 tq, 17 td, 18 ta      the quantisation / DC / AC table number (0 .. 3) of component c in bits 8 c .. 8 c + 7
- * status is int32 [B, 2]: the error code (0 = none; the codes of csrc/jpeg_decode.h) and the plan (0: one lane decodes the whole scan,
- * 1: one lane per restart interval).
+ *   19 ss_begin, 20 ss_count, 21 ss_bytes, 22 ss_wg_begin   the selfsync plan (below); all 0 in a file that does not take it.  23 is spare (0)
+ * status is int32 [B, 2]: the error code (0 = none; the codes of csrc/jpeg_decode.h) and, in bits 0 .. 1, the plan (0: one lane decodes
+ * the whole scan, 1: one lane per restart interval, 2: selfsync), in bit 2 the selfsync plan's fallback flag, in bits 8 .. 15 its launches.
  *   rf_jpeg_entropy_decode  : scans -> coef int16 [coef_blocks, 64], natural (de-zigzagged) order, zero-filled here.  ivl is int32
  *                             [2, nivl] (the file of each interval, ascending; then the offset of its first byte in the file's scan: 0 for
  *                             the first, 2 behind every FF D0..D7 for the others; ivl_host = the same words on the host).  One lane per
@@ -748,6 +749,27 @@ int rf_jpeg_pack(const void* slots_u8, int64_t slot_stride, const int* seg_bytes
 #define RF_JPEGDEC_MAX_SIDE 8192
 int rf_jpeg_entropy_decode(const void* comp_u8, int64_t comp_bytes, const int64_t* desc_host, const int64_t* desc, int B, const int* ivl_host,
                            const int* ivl, int nivl, int lanes, int16_t* coef, int64_t coef_blocks, int* status, void* stream);
+/*
+ * The self-synchronising plan (csrc/jpeg_sync.h) for files without DRI whose scan holds at least 2 * ss_bytes bytes: the scan is cut into
+ * ss_count = ceil(scan_len / ss_bytes) sub-sequences of ss_bytes (16 .. 65536) bytes, one lane each, 64 to a workgroup; ss_begin / ss_wg_begin
+ * are the file's first sub-sequence / workgroup among those of the batch (files in order, no gaps).  rf_jpeg_entropy_decode leaves such a
+ * file alone; rf_jpeg_selfsync_decode, called behind it on the same stream with the same arguments, decodes it to the same coefficients and
+ * the same error code.  `launches` (1 .. 16) sync launches iterate the lanes' start states towards their fixed point, which holds the
+ * serial decoder's own states; a file whose last launch still moved a workgroup boundary is decoded by the serial lane in a launch appended
+ * here (status word 1: plan 0 and the fallback flag), so the result never depends on `launches`.  `work` is device scratch of
+ * rf_jpeg_selfsync_work_bytes(sum of ss_count, sum of ceil(ss_count / 64), B) bytes, initialised here.  `stages` selects what is enqueued
+ * (RF_JPEGDEC_SS_ALL; the parts alone, in ascending order, for a caller that times them).
+ */
+#define RF_JPEGDEC_SS_SYNC 1
+#define RF_JPEGDEC_SS_SCAN 2
+#define RF_JPEGDEC_SS_WRITE 4
+#define RF_JPEGDEC_SS_DC 8
+#define RF_JPEGDEC_SS_SERIAL 16
+#define RF_JPEGDEC_SS_ALL 31
+int64_t rf_jpeg_selfsync_work_bytes(int64_t subseqs, int64_t workgroups, int B);
+int rf_jpeg_selfsync_decode(const void* comp_u8, int64_t comp_bytes, const int64_t* desc_host, const int64_t* desc, int B, const int* ivl_host,
+                            const int* ivl, int nivl, int lanes, int launches, int stages, void* work, int64_t work_bytes, int16_t* coef,
+                            int64_t coef_blocks, int* status, void* stream);
 int rf_jpeg_idct_u8(const int16_t* coef, int64_t coef_blocks, const void* comp_u8, int64_t comp_bytes, const int64_t* desc_host, const int64_t* desc,
                     int B, void* planes_u8, int64_t plane_bytes, const int* status, void* stream);
 int rf_jpeg_upsample_rgb_u8(const void* planes_u8, int64_t plane_bytes, const int64_t* desc_host, const int64_t* desc, int B, void* pix_u8,

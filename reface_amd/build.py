@@ -30,7 +30,7 @@ UNIT_DEPS = {"gemm_f16.hip": [os.path.join(CSRC, "gemm.hip")], "pasteback.hip": 
              # png_inflate.h: the zlib decoder core, compiled by hipcc here and by a host compiler into tests/pngdec_host_main.cpp
              "pngdec.hip": [os.path.join(CSRC, "png_inflate.h")],
              # jpeg_decode.h: the JPEG entropy-decoder core, compiled by hipcc here and by a host compiler into tests/jpegdec_host_main.cpp
-             "jpegdec.hip": [os.path.join(CSRC, "jpeg_decode.h")]}
+             "jpegdec.hip": [os.path.join(CSRC, "jpeg_decode.h"), os.path.join(CSRC, "jpeg_sync.h")]}
 
 
 

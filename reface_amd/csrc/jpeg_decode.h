@@ -115,8 +115,10 @@ struct Bits {
     }
 };
 
-// -> the symbol (0 .. 255), or -E_BAD_CODE / -E_TRUNCATED.  Consumes at least one bit.
-RF_JD int decode_symbol(Bits& br, const HuffTab* t) {
+// -> the symbol (0 .. 255), or -E_BAD_CODE / -E_TRUNCATED.  Consumes at least one bit, none where the code is bad.  `Reader` is Bits, or the
+// reader of csrc/jpeg_sync.h that knows its place in the stuffed scan: fill() leaves at least 25 bits in `acc`, take(n) says whether they were real.
+template <class Reader>
+RF_JD int decode_symbol(Reader& br, const HuffTab* t) {
     br.fill();
     const uint32_t lk = t->look[br.acc >> 24];
     int len = (int)(lk >> 8), sym = (int)(lk & 255u);
@@ -136,7 +138,8 @@ RF_JD int decode_symbol(Bits& br, const HuffTab* t) {
 }
 
 // s bits as a signed amplitude (T.81 F.2.2.1 EXTEND); 0 <= s <= 15.  -> false when the data ran out
-RF_JD bool receive_extend(Bits& br, int s, int32_t* v) {
+template <class Reader>
+RF_JD bool receive_extend(Reader& br, int s, int32_t* v) {
     br.fill();
     const int32_t raw = s ? (int32_t)(br.acc >> (32 - s)) : 0;
     *v = s && raw < (1 << (s - 1)) ? raw - (1 << s) + 1 : raw;

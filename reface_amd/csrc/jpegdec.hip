@@ -6,26 +6,35 @@
 //   rf_jpeg_idct_u8           dequantise + libjpeg's jpeg_idct_islow, 8 lanes per block: lane c takes column c, the workspace crosses
 //                             through LDS, lane r takes row r and stores its 8 samples as one 8-byte word.
 //   rf_jpeg_upsample_rgb_u8   one lane per pixel: libjpeg's fancy (triangle) chroma upsampling and its 16-bit YCbCr -> RGB.
-// All arithmetic is 32-bit integer.  Plain vector stores only.
+//   rf_jpeg_selfsync_decode   the self-synchronising plan of files without DRI (csrc/jpeg_sync.h): one lane per sub-sequence of L bytes.
+//                             `launches` x jpeg_sync_kernel (a workgroup = 64 sub-sequences of one file iterates to its own fixed point
+//                             in LDS, publishes its outgoing boundary state and returns at once when its incoming state is the one it last
+//                             ran with), jpeg_sync_scan_kernel (first block of every sub-sequence; a file whose last launch still moved a
+//                             boundary is flagged), jpeg_sync_write_kernel (coefficients, DC differences), jpeg_sync_dc_kernel (DC prefix
+//                             sums per component) and one more jpeg_entropy_decode_kernel in which the serial lane decodes flagged files.
+//                             No kernel waits for another workgroup: every one ends on its own bounds whatever the data.
+// All arithmetic is 32-bit integer.  Plain vector stores and ordinary atomics only.
 #include "common.h"
-#include "jpeg_decode.h"
+#include "jpeg_sync.h"
 
 namespace rf {
 using namespace jpgdec;
 
 __global__ __launch_bounds__(64) void jpeg_entropy_decode_kernel(const uint8_t* __restrict__ comp, const long long* __restrict__ desc, const int* __restrict__ ivl,
-                                                                 int nivl, int lanes, int16_t* __restrict__ coef, int* __restrict__ status) {
+                                                                 int nivl, int lanes, int16_t* __restrict__ coef, int* __restrict__ status, int fallback) {
     if ((int)threadIdx.x >= lanes) return;
     const long long g = (long long)blockIdx.x * lanes + threadIdx.x;
     if (g >= nivl) return;
     const int f = ivl[g];
     const long long* d = desc + (long long)f * DESC;
+    // a file of the selfsync plan is not this launch's; in the launch appended behind that plan the lane decodes it if it was flagged
+    if ((d[D_SS_COUNT] > 0) != (fallback != 0) || (fallback && !(status[2 * f + 1] & ST_FALLBACK))) return;
     const long long k = g - d[D_IVL_BEGIN], found = d[D_IVL_COUNT];
     const Geometry geo = geometry((int)d[D_H], (int)d[D_W], (int)d[D_NCOMP], (int)d[D_HS], (int)d[D_VS]);
     const long long expected = geo.intervals(d[D_RI]);
     const uint8_t* scan = comp + d[D_SCAN_OFF];
     const int* starts = ivl + nivl + d[D_IVL_BEGIN];
-    if (k == 0) status[2 * f + 1] = d[D_RI] > 0 ? 1 : 0;
+    if (k == 0 && !fallback) status[2 * f + 1] = d[D_RI] > 0 ? 1 : 0;
     int rc = check_interval(scan, starts, k, found, expected);
     if (rc == OK) {
         const uint32_t begin = (uint32_t)starts[k];
@@ -33,6 +42,212 @@ __global__ __launch_bounds__(64) void jpeg_entropy_decode_kernel(const uint8_t* 
         rc = decode_interval(scan, begin, end, d, comp + d[D_TAB_OFF], k, coef + d[D_COEF_OFF] * 64);
     }
     if (rc != OK) atomicCAS(&status[2 * f], 0, rc);          // the first code stays
+}
+
+// ------------------------------------------------------------------------------------------------ the selfsync plan (csrc/jpeg_sync.h)
+// The work buffer of a batch with S sub-sequences in G workgroups: the states (slot i = the state sub-sequence i starts from; written by
+// the lane of i - 1 alone), the incoming state every workgroup last ran with, the lowest (sub-sequence << 8 | code) of a file's write
+// pass, the first block of every sub-sequence, its block count, and a "a boundary moved" word per file and launch.
+struct SsWork {
+    uint64_t* state;
+    uint64_t* seen;
+    unsigned long long* err;
+    long long* first;
+    int* cnt;
+    int* chg;
+};
+static SsWork ss_work(void* base, int64_t S, int64_t G, int64_t B) {
+    SsWork w;
+    w.state = (uint64_t*)base;
+    w.seen = w.state + S;
+    w.err = (unsigned long long*)(w.seen + G);
+    w.first = (long long*)(w.err + B);
+    w.cnt = (int*)(w.first + S);
+    w.chg = w.cnt + S;
+    return w;
+}
+static int64_t ss_work_bytes(int64_t S, int64_t G, int64_t B) { return 8 * (S + G + B + S) + 4 * (S + B * SS_MAX_LAUNCHES); }
+
+__device__ __forceinline__ uint64_t ss_load(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void ss_store(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the file's 8 Huffman tables into LDS: 7296 bytes = 1824 words, 29 per lane
+__device__ __forceinline__ void ss_stage_tables(HuffTab* tabs, const uint8_t* __restrict__ comp, const long long* d, int lane, int lanes) {
+    const uint32_t* src = (const uint32_t*)(comp + d[D_TAB_OFF] + QUANT_BYTES);          // tab_off is a multiple of 16
+    uint32_t* dst = (uint32_t*)tabs;
+    for (int i = lane; i < 8 * (int)sizeof(HuffTab) / 4; i += lanes) dst[i] = src[i];
+    __syncthreads();
+}
+
+// One workgroup = sub-sequences [64 x, 64 x + 64) of file y.  A Jacobi pass evaluates F for every lane whose input moved; 64 passes
+// reach the workgroup's fixed point from any start, because pass t makes the input of lane t final.
+__global__ __launch_bounds__(SS_LANES) void jpeg_sync_kernel(const uint8_t* __restrict__ comp, const long long* __restrict__ desc, SsWork w, int launch) {
+    __shared__ HuffTab tabs[8];
+    __shared__ uint64_t sh[SS_LANES + 1];
+    const int f = blockIdx.y, lane = threadIdx.x;
+    const long long* d = desc + (long long)f * DESC;
+    const long long n = d[D_SS_COUNT], g0 = (long long)blockIdx.x * SS_LANES, gi = g0 + lane;
+    if (g0 >= n || d[D_IVL_COUNT] != 1) return;
+    const uint64_t L = (uint64_t)d[D_SS_BYTES];
+    const uint32_t len = (uint32_t)d[D_SCAN_LEN];
+    const uint8_t* scan = comp + d[D_SCAN_OFF];
+    uint64_t* st = w.state + d[D_SS_BEGIN];
+    int* cnt = w.cnt + d[D_SS_BEGIN];
+    uint64_t* seen = w.seen + d[D_SS_WG_BEGIN] + blockIdx.x;
+    const uint64_t before = *seen;
+    uint64_t incoming = blockIdx.x == 0 ? 0ull : ss_load(st + g0);
+    if (incoming == SS_NEVER) incoming = ss_guess(scan, len, (uint64_t)g0 * L);
+    const bool first_run = before == SS_NEVER;
+    if (!first_run && incoming == before) return;          // (uniform) nothing moved in front of this workgroup since it last ran
+    ss_stage_tables(tabs, comp, d, lane, SS_LANES);
+    const SsFile file = ss_file(scan, d, tabs);
+    const bool live = gi < n;
+    const uint64_t bound = 8ull * (((uint64_t)gi + 1) * L < len ? ((uint64_t)gi + 1) * L : len);
+    int mycnt = 0;
+    uint64_t old_out = 0;
+    if (live) {
+        sh[lane] = lane == 0 ? incoming : (first_run ? ss_guess(scan, len, (uint64_t)gi * L) : st[gi]);
+        if (!first_run) mycnt = cnt[gi];
+    } else {
+        sh[lane] = 0;
+    }
+    if (lane == SS_LANES - 1) {
+        if (gi + 1 < n) {
+            old_out = ss_load(st + gi + 1);
+            if (old_out == SS_NEVER) old_out = ss_guess(scan, len, (uint64_t)(gi + 1) * L);
+        }
+        sh[SS_LANES] = old_out;
+    }
+    __syncthreads();
+    bool dirty = live && (first_run || lane == 0);
+    for (int pass = 0; pass < SS_LANES; ++pass) {          // 64 passes at the most
+        const uint64_t in = sh[lane];
+        uint64_t out = 0;
+        bool moved = false;
+        if (dirty) {
+            out = ss_eval(file, in, bound, &mycnt);
+            moved = out != sh[lane + 1];
+        }
+        __syncthreads();          // every lane has read its input and its neighbour's
+        if (moved) sh[lane + 1] = out;
+        const int any = __syncthreads_or(moved ? 1 : 0);
+        dirty = live && lane > 0 && sh[lane] != in;
+        if (!any) break;
+    }
+    if (live) {
+        cnt[gi] = mycnt;
+        if (gi + 1 < n) {
+            if (lane < SS_LANES - 1) {
+                st[gi + 1] = sh[lane + 1];
+            } else {          // the outgoing boundary: the next workgroup's incoming state
+                ss_store(st + gi + 1, sh[SS_LANES]);
+                if (sh[SS_LANES] != old_out) atomicOr(&w.chg[f * SS_MAX_LAUNCHES + launch], 1);
+            }
+        }
+    }
+    if (lane == 0) *seen = incoming;
+}
+
+// One workgroup per file: the exclusive prefix sum of the block counts; the plan, the fallback flag and the launches that were needed
+// into status word 1.  A file with restart markers and no DRI is the serial plan's E_RST_COUNT.
+__global__ __launch_bounds__(256) void jpeg_sync_scan_kernel(const long long* __restrict__ desc, SsWork w, int launches, int* __restrict__ status) {
+    __shared__ long long part[256];
+    const int f = blockIdx.x, t = threadIdx.x;
+    const long long* d = desc + (long long)f * DESC;
+    const long long n = d[D_SS_COUNT];
+    if (n <= 0) return;
+    const int* chg = w.chg + f * SS_MAX_LAUNCHES;
+    int last = -1;
+    for (int k = 0; k < launches; ++k) last = chg[k] ? k : last;          // <= 16
+    const bool fallback = last == launches - 1 && d[D_IVL_COUNT] == 1;
+    if (t == 0) {
+        const int used = last + 2 < launches ? last + 2 : launches;
+        status[2 * f + 1] = (fallback ? ST_FALLBACK : PLAN_SELFSYNC) | (used << ST_LAUNCHES_SHIFT);
+        if (d[D_IVL_COUNT] != 1) status[2 * f] = E_RST_COUNT;
+    }
+    if (fallback || d[D_IVL_COUNT] != 1) return;
+    const int* cnt = w.cnt + d[D_SS_BEGIN];
+    long long* first = w.first + d[D_SS_BEGIN];
+    const long long chunk = (n + 255) / 256, a = t * chunk, b = a + chunk < n ? a + chunk : n;
+    long long sum = 0;
+    for (long long i = a; i < b; ++i) sum += cnt[i];          // <= chunk
+    part[t] = sum;
+    __syncthreads();
+    if (t == 0) {
+        long long run = 0;
+        for (int i = 0; i < 256; ++i) {
+            const long long v = part[i];
+            part[i] = run;
+            run += v;
+        }
+    }
+    __syncthreads();
+    long long run = part[t];
+    for (long long i = a; i < b; ++i) {
+        first[i] = run;
+        run += cnt[i];
+    }
+}
+
+__global__ __launch_bounds__(SS_LANES) void jpeg_sync_write_kernel(const uint8_t* __restrict__ comp, const long long* __restrict__ desc, SsWork w,
+                                                                   int16_t* __restrict__ coef, const int* __restrict__ status) {
+    __shared__ HuffTab tabs[8];
+    const int f = blockIdx.y, lane = threadIdx.x;
+    const long long* d = desc + (long long)f * DESC;
+    const long long n = d[D_SS_COUNT], g0 = (long long)blockIdx.x * SS_LANES, gi = g0 + lane;
+    if (g0 >= n || d[D_IVL_COUNT] != 1 || (status[2 * f + 1] & ST_FALLBACK)) return;          // (uniform)
+    const Geometry geo = geometry((int)d[D_H], (int)d[D_W], (int)d[D_NCOMP], (int)d[D_HS], (int)d[D_VS]);
+    const long long blocks = geo.blocks();
+    if (w.first[d[D_SS_BEGIN] + g0] >= blocks) return;          // (uniform) the first blocks ascend
+    ss_stage_tables(tabs, comp, d, lane, SS_LANES);
+    if (gi >= n) return;
+    const uint64_t L = (uint64_t)d[D_SS_BYTES];
+    const uint32_t len = (uint32_t)d[D_SCAN_LEN];
+    const SsFile file = ss_file(comp + d[D_SCAN_OFF], d, tabs);
+    const uint64_t bound = 8ull * (((uint64_t)gi + 1) * L < len ? ((uint64_t)gi + 1) * L : len);
+    const uint64_t s = gi == 0 ? 0ull : w.state[d[D_SS_BEGIN] + gi];
+    const int rc = ss_write(file, s, bound, gi == n - 1, w.first[d[D_SS_BEGIN] + gi], blocks, coef + d[D_COEF_OFF] * 64);
+    if (rc != OK) atomicMin(&w.err[f], ((unsigned long long)gi << 8) | (unsigned long long)rc);          // the lowest sub-sequence's code: that lane began at a true state
+}
+
+// DC differences -> DC values: block (c, file) sums the differences of component c in scan order, mod 2^32 as decode_block does, and
+// stores them as int16.  Block (0, file) first hands the write pass's code to the status word.
+__global__ __launch_bounds__(256) void jpeg_sync_dc_kernel(const long long* __restrict__ desc, SsWork w, int16_t* __restrict__ coef, int* __restrict__ status) {
+    __shared__ uint32_t part[256];
+    const int f = blockIdx.y, c = blockIdx.x, t = threadIdx.x;
+    const long long* d = desc + (long long)f * DESC;
+    if (d[D_SS_COUNT] <= 0 || d[D_IVL_COUNT] != 1 || (status[2 * f + 1] & ST_FALLBACK)) return;
+    const unsigned long long e = w.err[f];
+    if (e != ~0ull) {
+        if (c == 0 && t == 0) atomicCAS(&status[2 * f], 0, (int)(e & 255ull));
+        return;
+    }
+    const int ncomp = (int)d[D_NCOMP];
+    if (c >= ncomp) return;
+    const Geometry geo = geometry((int)d[D_H], (int)d[D_W], ncomp, (int)d[D_HS], (int)d[D_VS]);
+    const int ny = ncomp == 3 ? (int)(d[D_HS] * d[D_VS]) : 1;
+    const long long nb = geo.mcus() * (c == 0 ? ny : 1);
+    int16_t* cf = coef + d[D_COEF_OFF] * 64;
+    const long long chunk = (nb + 255) / 256, a = t * chunk, b = a + chunk < nb ? a + chunk : nb;
+    uint32_t sum = 0;
+    for (long long i = a; i < b; ++i) sum += (uint32_t)(int32_t)cf[ss_block_of(i, c, ny, geo.bpm) * 64];          // <= chunk
+    part[t] = sum;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t run = 0;
+        for (int i = 0; i < 256; ++i) {
+            const uint32_t v = part[i];
+            part[i] = run;
+            run += v;
+        }
+    }
+    __syncthreads();
+    uint32_t pred = part[t];
+    for (long long i = a; i < b; ++i) {
+        int16_t* o = cf + ss_block_of(i, c, ny, geo.bpm) * 64;
+        pred += (uint32_t)(int32_t)*o;
+        *o = (int16_t)pred;
+    }
 }
 
 // jpeg_idct_islow's 1-D pass on 8 values held in registers (CONST_BITS 13); the caller descales.  Products wrap as unsigned: hostile
@@ -237,8 +452,67 @@ extern "C" int rf_jpeg_entropy_decode(const void* comp_u8, int64_t comp_bytes, c
         return 2;
     }
     const unsigned grid = (unsigned)((nivl + lanes - 1) / lanes);
-    hipLaunchKernelGGL(jpeg_entropy_decode_kernel, dim3(grid), dim3(64), 0, st, (const uint8_t*)comp_u8, (const long long*)desc, ivl, nivl, lanes, coef, status);
+    hipLaunchKernelGGL(jpeg_entropy_decode_kernel, dim3(grid), dim3(64), 0, st, (const uint8_t*)comp_u8, (const long long*)desc, ivl, nivl, lanes, coef, status, 0);
     RF_LAUNCH_CHECK("rf_jpeg_entropy_decode");
+    return 0;
+}
+
+extern "C" int64_t rf_jpeg_selfsync_work_bytes(int64_t subseqs, int64_t workgroups, int B) {
+    return subseqs < 0 || workgroups < 0 || B < 0 ? -1 : ss_work_bytes(subseqs, workgroups, B);
+}
+
+extern "C" int rf_jpeg_selfsync_decode(const void* comp_u8, int64_t comp_bytes, const int64_t* desc_host, const int64_t* desc, int B, const int* ivl_host, const int* ivl,
+                                       int nivl, int lanes, int launches, int stages, void* work, int64_t work_bytes, int16_t* coef, int64_t coef_blocks, int* status,
+                                       void* stream) {
+    RF_CHECK(comp_u8 && desc_host && desc && ivl_host && ivl && work && coef && status && B > 0 && B <= 65535 && nivl >= B && lanes >= 1 && lanes <= 64,
+             "rf_jpeg_selfsync_decode: bad arguments (B=%d nivl=%d lanes=%d)", B, nivl, lanes);
+    RF_CHECK(launches >= 1 && launches <= SS_MAX_LAUNCHES && stages >= 1 && stages <= RF_JPEGDEC_SS_ALL, "rf_jpeg_selfsync_decode: 1 <= launches <= %d, 1 <= stages <= %d",
+             SS_MAX_LAUNCHES, RF_JPEGDEC_SS_ALL);
+    RF_CHECK(((uintptr_t)comp_u8 & 15) == 0 && ((uintptr_t)work & 7) == 0 && coef_blocks > 0 && coef_blocks < (1ll << 31),
+             "rf_jpeg_selfsync_decode: comp must be 16-byte, work 8-byte aligned, 0 < coef_blocks < 2^31");
+    int64_t S = 0, G = 0, maxn = 0, next = 0;
+    for (int f = 0; f < B; ++f) {
+        const int64_t* d = desc_host + (int64_t)f * DESC;
+        RF_CHECK(jpegdec_desc_ok(d, comp_bytes, coef_blocks, 1ll << 62, 0, false), "rf_jpeg_selfsync_decode: descriptor %d is out of range", f);
+        const int64_t ib = d[D_IVL_BEGIN], in = d[D_IVL_COUNT];          // (the serial lane of the last launch reads them)
+        RF_CHECK(in >= 1 && ib == next && ib + in <= nivl, "rf_jpeg_selfsync_decode: the intervals of file %d are not the next %lld of %d", f, (long long)in, nivl);
+        for (int64_t k = ib; k < ib + in; ++k) {
+            const int64_t s = ivl_host[nivl + k];
+            RF_CHECK(ivl_host[k] == f && (k == ib ? s == 0 : (s >= 2 && s >= ivl_host[nivl + k - 1] + 2 && s <= d[D_SCAN_LEN])),
+                     "rf_jpeg_selfsync_decode: interval %lld of file %d is out of range or out of order", (long long)(k - ib), f);
+        }
+        next = ib + in;
+        const int64_t n = d[D_SS_COUNT], L = d[D_SS_BYTES];
+        if (n == 0) continue;
+        RF_CHECK(L >= SS_MIN_BYTES && L <= SS_MAX_BYTES && d[D_RI] == 0 && d[D_SCAN_LEN] >= 2 * L && n == (d[D_SCAN_LEN] + L - 1) / L && d[D_SS_BEGIN] == S &&
+                     d[D_SS_WG_BEGIN] == G,
+                 "rf_jpeg_selfsync_decode: the sub-sequences of file %d (%lld of %lld bytes from slot %lld, workgroup %lld) do not fit its scan or the batch", f, (long long)n,
+                 (long long)L, (long long)d[D_SS_BEGIN], (long long)d[D_SS_WG_BEGIN]);
+        S += n;
+        G += (n + SS_LANES - 1) / SS_LANES;
+        maxn = n > maxn ? n : maxn;
+    }
+    RF_CHECK(S > 0 && S < (1ll << 31), "rf_jpeg_selfsync_decode: no file of the batch takes the plan (or 2^31 sub-sequences)");
+    RF_CHECK(work_bytes >= ss_work_bytes(S, G, B), "rf_jpeg_selfsync_decode: work holds %lld bytes, %lld are needed", (long long)work_bytes, (long long)ss_work_bytes(S, G, B));
+    const SsWork w = ss_work(work, S, G, B);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((maxn + SS_LANES - 1) / SS_LANES), (unsigned)B);
+    if (stages & RF_JPEGDEC_SS_SYNC) {
+        // no state, no workgroup has run, no error; then no boundary has moved
+        if (hipMemsetAsync(work, 0xFF, (size_t)ss_work_bytes(S, G, B), st) != hipSuccess || hipMemsetAsync(w.chg, 0, (size_t)B * SS_MAX_LAUNCHES * 4, st) != hipSuccess) {
+            rf::set_error("rf_jpeg_selfsync_decode: hipMemsetAsync failed");
+            return 2;
+        }
+        for (int k = 0; k < launches; ++k) hipLaunchKernelGGL(jpeg_sync_kernel, grid, dim3(SS_LANES), 0, st, (const uint8_t*)comp_u8, (const long long*)desc, w, k);
+    }
+    if (stages & RF_JPEGDEC_SS_SCAN) hipLaunchKernelGGL(jpeg_sync_scan_kernel, dim3((unsigned)B), dim3(256), 0, st, (const long long*)desc, w, launches, status);
+    if (stages & RF_JPEGDEC_SS_WRITE)
+        hipLaunchKernelGGL(jpeg_sync_write_kernel, grid, dim3(SS_LANES), 0, st, (const uint8_t*)comp_u8, (const long long*)desc, w, coef, (const int*)status);
+    if (stages & RF_JPEGDEC_SS_DC) hipLaunchKernelGGL(jpeg_sync_dc_kernel, dim3(3, (unsigned)B), dim3(256), 0, st, (const long long*)desc, w, coef, status);
+    if (stages & RF_JPEGDEC_SS_SERIAL)
+        hipLaunchKernelGGL(jpeg_entropy_decode_kernel, dim3((unsigned)((nivl + lanes - 1) / lanes)), dim3(64), 0, st, (const uint8_t*)comp_u8, (const long long*)desc, ivl, nivl,
+                           lanes, coef, status, 1);
+    RF_LAUNCH_CHECK("rf_jpeg_selfsync_decode");
     return 0;
 }
 

@@ -17,8 +17,13 @@ every other SOFn, 12-bit, 4 components, an Adobe APP14 marker whose transform is
 RGB to ``L``, larger images, anything that is no JPEG at all -- is decoded by PIL on the host, file by file, counted and named with a
 reason (``job.report``), so ``decode`` gives PIL's array or PIL's exception.
 
-Two plans (``job.report[i]["plan"]``): ``"intervals"``, one lane per restart interval, as the files ``JpegEncoder`` / ``--write_video``
-write (one interval per MCU row) decode, and ``"serial"``, one lane for the whole scan of a file without DRI.
+Three plans (``job.report[i]["plan"]``): ``"intervals"``, one lane per restart interval, as the files ``JpegEncoder`` / ``--write_video``
+write (one interval per MCU row) decode; ``"serial"``, one lane for the whole scan of a file without DRI; and, opt-in
+(``JpegDecoder(parallel=True)``, the callers' ``--gpu_jpeg_parallel``), ``"selfsync"`` for files without DRI whose scan holds at least two
+sub-sequences of ``subseq_bytes``: one lane per sub-sequence decodes from a guessed bit offset, ``sync_launches`` launches iterate the
+lanes' start states to their fixed point -- which holds the serial decoder's own states (csrc/jpeg_sync.h) -- and a write pass decodes every
+sub-sequence from its true state.  A file whose last launch still moved a state is decoded by the serial lane after all
+(``report[i]["fallback"]``), so the pixels never depend on the settings.
 
 ``JpegDecoder.decode_async`` enqueues everything on the current stream and returns at once; ``JpegDecodeJob.result()`` waits for the
 event, reads the per-file error codes and raises ``JpegDecodeError`` naming the file for a damaged scan.
@@ -37,7 +42,12 @@ DESC = 24                                   # RF_JPEGDEC_DESC
 HUFF_BYTES = 912                            # sizeof(HuffTab) in csrc/jpeg_decode.h
 TABLE_BYTES = 512 + 8 * HUFF_BYTES          # RF_JPEGDEC_TABLE_BYTES
 MAX_SIDE = 8192                             # RF_JPEGDEC_MAX_SIDE: 128 bytes of coefficients per block, 200 MB for one 8192 x 8192 file at 4:2:0
-PLANS = ("serial", "intervals")
+PLANS = ("serial", "intervals", "selfsync")
+SS_LANES, SS_MIN_BYTES, SS_MAX_BYTES, SS_MAX_LAUNCHES = 64, 16, 1 << 16, 16          # csrc/jpeg_sync.h
+SS_SYNC, SS_SCAN, SS_WRITE, SS_DC, SS_SERIAL, SS_ALL = 1, 2, 4, 8, 16, 31           # RF_JPEGDEC_SS_*
+ST_FALLBACK, ST_LAUNCHES_SHIFT = 4, 8                                               # status word 1 behind the plan
+SUBSEQ_BYTES = 128                          # the defaults of the selfsync plan (the sweep)
+SYNC_LAUNCHES = 4
 ERRORS = {1: "the scan is truncated", 2: "invalid Huffman code", 3: "coefficient index past 63", 4: "wrong number of restart intervals",
           5: "restart markers out of order", 6: "invalid DC category", 7: "iteration cap reached"}
 _ZZ = np.array(M.ZIGZAG)
@@ -275,6 +285,19 @@ def counts_line(decoder, what="files"):
     return f"gpu_jpeg_decode: {decoder.counts['gpu']} {what} decoded on the device, {decoder.counts['host']} on the host"
 
 
+def subseqs_of(info, subseq_bytes):
+    """The sub-sequences of a device file under the selfsync plan, 0 where it keeps the plan it has (DRI, or a scan below two of them)."""
+    return -(-info.scan[1] // subseq_bytes) if info.ri == 0 and info.scan[1] >= 2 * subseq_bytes else 0
+
+
+def _selfsync_settings(subseq_bytes, sync_launches):
+    if not SS_MIN_BYTES <= subseq_bytes <= SS_MAX_BYTES:          # (16: a symbol with its stuffing never spans a whole sub-sequence)
+        raise ValueError(f"JpegDecoder: subseq_bytes must be {SS_MIN_BYTES} .. {SS_MAX_BYTES}, got {subseq_bytes}")
+    if not 1 <= sync_launches <= SS_MAX_LAUNCHES:
+        raise ValueError(f"JpegDecoder: sync_launches must be 1 .. {SS_MAX_LAUNCHES}, got {sync_launches}")
+    return int(subseq_bytes), int(sync_launches)
+
+
 def _up16(n):
     return (n + 15) // 16 * 16
 
@@ -307,13 +330,21 @@ class _Launched:
         self.__dict__.update(kw)
 
 
+def _status_report(code, word, subseqs):
+    """The report fields the two status words of a file give; `subseqs` > 0 for a file that was given to the selfsync plan."""
+    r = {"plan": PLANS[word & 3], "code": code}
+    if subseqs:
+        r.update(subseqs=subseqs, launches_used=(word >> ST_LAUNCHES_SHIFT) & 255, fallback=bool(word & ST_FALLBACK))
+    return r
+
+
 class JpegDecodeJob:
     """One enqueued decode; ``result()`` (any thread, once) gives the uint8 device tensors [H, W, C] in the order of the items, ``report``
     (complete after ``result()``) says per file where it was decoded, by which plan and, on the host, why."""
 
-    def __init__(self, dec, names, outs, gpu_idx, status, event, staging, keep, report):
+    def __init__(self, dec, names, outs, gpu_idx, status, event, staging, keep, report, subseqs=None):
         self.dec, self.names, self.outs, self.gpu_idx, self.status, self.event = dec, names, outs, gpu_idx, status, event
-        self.staging, self.keep, self.report = staging, keep, report
+        self.staging, self.keep, self.report, self.subseqs = staging, keep, report, subseqs
         self.batch = None          # the [B, H, W, C] tensor the images are views of, when all of them came from the device at one shape
 
     def discard(self):
@@ -332,8 +363,7 @@ class JpegDecodeJob:
                 self.event.synchronize()
                 st = self.status.cpu().tolist()
                 for k, i in enumerate(self.gpu_idx):
-                    self.report[i]["plan"] = PLANS[st[2 * k + 1] & 1]
-                    self.report[i]["code"] = st[2 * k]
+                    self.report[i].update(_status_report(st[2 * k], st[2 * k + 1], self.subseqs[k] if self.subseqs else 0))
                 for k, i in enumerate(self.gpu_idx):
                     if st[2 * k] != 0:
                         raise JpegDecodeError(self.names[i], st[2 * k])
@@ -345,12 +375,13 @@ class JpegDecodeJob:
 class JpegDecoder:
     """``decode(items, mode=None) -> list of uint8 device tensors [H, W, C]`` (C = 1 for grey): items are paths, ``bytes`` or
     ``(name, bytes)``; ``mode`` in (None, "RGB", "L") reproduces ``Image.open(p)`` and ``.convert(mode)``.  Files of any sizes and of both
-    routes may share a call."""
+    routes may share a call.  ``parallel`` gives files without DRI the selfsync plan (``subseq_bytes`` per lane, ``sync_launches`` launches)."""
 
     MAX_FREE = 4
     WAVES = 1024          # lanes per wave are chosen so that a launch has about this many waves (256 CUs x 4 SIMDs) before waves fill up
 
-    def __init__(self, device="cuda"):
+    def __init__(self, device="cuda", parallel=False, subseq_bytes=SUBSEQ_BYTES, sync_launches=SYNC_LAUNCHES):
+        self.parallel, (self.subseq_bytes, self.sync_launches) = bool(parallel), _selfsync_settings(subseq_bytes, sync_launches)
         self.device = torch.device(device)
         self._free, self._lock = [], threading.Lock()
         self.counts = {"gpu": 0, "host": 0}          # files decoded so far, by where (the callers print them)
@@ -369,7 +400,7 @@ class JpegDecoder:
             if len(self._free) < self.MAX_FREE:
                 self._free.append(s)
 
-    def _launch(self, datas, infos, out_cs, misalign=0, timing=False, stages=3):
+    def _launch(self, datas, infos, out_cs, misalign=0, timing=False, stages=3, parallel=None, subseq_bytes=None, sync_launches=None):
         """Enqueue the decode of device-eligible files.  `misalign` (tests) shifts every scan off its 16-byte aligned place in the upload;
         `timing` records an event around every kernel; `stages` < 3 stops behind the entropy decode (1) or the IDCT (2)."""
         lib = _lib.load()
@@ -405,12 +436,18 @@ class JpegDecoder:
         comp0 = desc_bytes + ivl_bytes
         for blk, off in blocks.items():
             sg.a[comp0 + off:comp0 + off + TABLE_BYTES] = np.frombuffer(blk, dtype=np.uint8)
-        ib = 0
+        # (the per-call switches of `coefficients` and the tests, checked like the constructor's)
+        L_ss, launches = _selfsync_settings(self.subseq_bytes if subseq_bytes is None else subseq_bytes, self.sync_launches if sync_launches is None else sync_launches)
+        subseqs = [subseqs_of(info, L_ss) if (self.parallel if parallel is None else parallel) else 0 for info in infos]
+        ib = ss = wg = 0
         pack = lambda t: sum(int(v) << (8 * c) for c, v in enumerate(t))          # noqa: E731
         for b, (data, info, c) in enumerate(zip(datas, infos, out_cs)):
             ni = len(info.starts)
             desc[b] = (scan_off[b], info.scan[1], info.height, info.width, info.ncomp, info.hs, info.vs, info.ri, coef_off[b], plane_off[b], c, pix_off[b],
-                       info.width * c, blocks[table_block(info)], ib, ni, pack(info.tq), pack(info.td), pack(info.ta), 0, 0, 0, 0, 0)
+                       info.width * c, blocks[table_block(info)], ib, ni, pack(info.tq), pack(info.td), pack(info.ta),
+                       *((ss, subseqs[b], L_ss, wg) if subseqs[b] else (0, 0, 0, 0)), 0)
+            ss += subseqs[b]
+            wg += -(-subseqs[b] // SS_LANES)
             ivl[0, ib:ib + ni] = b
             ivl[1, ib:ib + ni] = info.starts
             ib += ni
@@ -428,7 +465,7 @@ class JpegDecoder:
             status = torch.empty(2 * B, dtype=torch.int32, device=dev)
             base = up.data_ptr()
             comp_ptr = base + comp0
-            evs = []
+            evs, names, keep_work = [], ["entropy_decode"], ()
 
             def mark():
                 if timing:
@@ -439,20 +476,32 @@ class JpegDecoder:
             _lib.check(lib.rf_jpeg_entropy_decode(comp_ptr, comp_bytes, desc.ctypes.data, base, B, ivl.ctypes.data, base + desc_bytes, nivl, lanes,
                                                   coef.data_ptr(), cb, status.data_ptr(), st.cuda_stream), "rf_jpeg_entropy_decode")
             mark()
+            if ss:          # the selfsync plan of the files the launch above left alone; one call, or its parts with an event behind each
+                nwork = lib.rf_jpeg_selfsync_work_bytes(ss, wg, B)
+                work = torch.empty(nwork, dtype=torch.uint8, device=dev)
+                for part in ((SS_SYNC, SS_SCAN, SS_WRITE, SS_DC, SS_SERIAL) if timing else (SS_ALL,)):
+                    _lib.check(lib.rf_jpeg_selfsync_decode(comp_ptr, comp_bytes, desc.ctypes.data, base, B, ivl.ctypes.data, base + desc_bytes, nivl, lanes,
+                                                           launches, part, work.data_ptr(), nwork, coef.data_ptr(), cb, status.data_ptr(),
+                                                           st.cuda_stream), "rf_jpeg_selfsync_decode")
+                    mark()
+                names += ["sync", "subseq_scan", "write", "dc_prefix", "serial_fallback"]
+                keep_work = (work,)
             if stages >= 2:
                 _lib.check(lib.rf_jpeg_idct_u8(coef.data_ptr(), cb, comp_ptr, comp_bytes, desc.ctypes.data, base, B, planes.data_ptr(), planes.numel(),
                                                status.data_ptr(), st.cuda_stream), "rf_jpeg_idct_u8")
                 mark()
+                names.append("idct")
             if stages >= 3:
                 _lib.check(lib.rf_jpeg_upsample_rgb_u8(planes.data_ptr(), planes.numel(), desc.ctypes.data, base, B, pix.data_ptr(), pix.numel(),
                                                        status.data_ptr(), st.cuda_stream), "rf_jpeg_upsample_rgb_u8")
                 mark()
+                names.append("upsample_rgb")
             ev = torch.cuda.Event()
             ev.record(st)
         images = [pix[pix_off[b]:pix_off[b] + i.height * i.width * c].view(i.height, i.width, c) for b, (i, c) in enumerate(zip(infos, out_cs))]
         batch = pix.view(B, infos[0].height, infos[0].width, out_cs[0]) if same else None
-        return _Launched(images=images, status=status, event=ev, staging=sg, keep=(up, coef, planes, pix), batch=batch, coef=coef, coef_off=coef_off,
-                         planes=planes, plane_off=plane_off, events=evs, lanes=lanes, nivl=nivl)
+        return _Launched(images=images, status=status, event=ev, staging=sg, keep=(up, coef, planes, pix) + keep_work, batch=batch, coef=coef,
+                         coef_off=coef_off, planes=planes, plane_off=plane_off, events=evs, event_names=names, lanes=lanes, nivl=nivl, subseqs=subseqs)
 
     def decode_async(self, items, mode=None):
         _out_channels(1, mode)
@@ -494,7 +543,7 @@ class JpegDecoder:
         L = self._launch([datas[i] for i in gpu_idx], infos, out_cs)
         for k, i in enumerate(gpu_idx):
             outs[i] = L.images[k]
-        job = JpegDecodeJob(self, names, outs, gpu_idx, L.status, L.event, L.staging, L.keep, report)
+        job = JpegDecodeJob(self, names, outs, gpu_idx, L.status, L.event, L.staging, L.keep, report, L.subseqs)
         job.batch = L.batch if len(gpu_idx) == len(datas) else None
         return job
 
@@ -502,20 +551,21 @@ class JpegDecoder:
         return self.decode_async(items, mode).result()
 
     # ---- the stages alone (tests, tools/jpegdec_rate.py)
-    def coefficients(self, files, misalign=0, check=True):
+    def coefficients(self, files, misalign=0, check=True, parallel=None, subseq_bytes=None, sync_launches=None):
         """Device-eligible files (bytes) -> (list of int16 device tensors [blocks, 64] in natural order, report): the entropy decode alone.
-        A damaged scan raises JpegDecodeError naming its index, or, with check=False, only leaves its code in the report."""
+        A damaged scan raises JpegDecodeError naming its index, or, with check=False, only leaves its code in the report.  The three
+        switches of the constructor may be given for this call."""
         infos = [parse_jpeg(f) for f in files]
         for k, i in enumerate(infos):
             if i.route != "gpu":
                 raise ValueError(f"<file #{k}>: not a device file ({i.reason})")
-        L = self._launch(files, infos, [i.ncomp for i in infos], misalign=misalign, stages=1)
+        L = self._launch(files, infos, [i.ncomp for i in infos], misalign=misalign, stages=1, parallel=parallel, subseq_bytes=subseq_bytes, sync_launches=sync_launches)
         try:
             L.event.synchronize()
             st = L.status.cpu().tolist()
         finally:
             self._release(L.staging)
-        report = [{"where": "gpu", "plan": PLANS[st[2 * k + 1] & 1], "code": st[2 * k]} for k in range(len(files))]
+        report = [{"where": "gpu", **_status_report(st[2 * k], st[2 * k + 1], L.subseqs[k])} for k in range(len(files))]
         for k in range(len(files)):
             if check and st[2 * k] != 0:
                 raise JpegDecodeError(f"<file #{k}>", st[2 * k])
@@ -537,10 +587,10 @@ class FileDecoder:
     item to the decoder of its signature; a file of a kind that is not enabled, or of neither kind, is decoded by PIL.  ``kinds`` is what
     ``pngdec.ByteFolder`` asks to know which files travel as bytes."""
 
-    def __init__(self, device="cuda", png=False, jpeg=False):
+    def __init__(self, device="cuda", png=False, jpeg=False, jpeg_parallel=False):
         self.device = torch.device(device)
         self.png = pngdec.PngDecoder(device) if png else None
-        self.jpeg = JpegDecoder(device) if jpeg else None
+        self.jpeg = JpegDecoder(device, parallel=jpeg_parallel) if jpeg else None
         self.kinds = tuple(k for k, d in (("png", self.png), ("jpeg", self.jpeg)) if d is not None)
 
     def lines(self, what="files"):

@@ -145,12 +145,15 @@ def build_parser():
                    "Motion-JPEG AVI file (as --write_video writes them), decoded on the GPU (reface_amd/jpegdec.py) and used where "
                    "<Base_dir>/<video>/<i>.png is used otherwise; --landmarks index its frames.  With --write_video and no --video_fps the output "
                    "takes this file's rate")
+    p.add_argument("--gpu_jpeg_parallel", action="store_true", help="--video_in: frames without restart markers (an MJPG file of another writer) "
+                   "are decoded by one lane per sub-sequence of the scan (the self-synchronising plan of reface_amd/jpegdec.py) instead of one lane "
+                   "per frame; the frames are the same")
     p.add_argument("--video_quality", type=int, default=90, help="--write_video: libjpeg quality, 1 .. 100 (default 90)")
     p.add_argument("--video_subsampling", type=str, choices=["420", "444"], default="420", help="--write_video: chroma subsampling (default 420)")
     return p
 
 
-VIDEO_OPTIONS = ("write_video", "video_fps", "video_quality", "video_subsampling", "video_in")
+VIDEO_OPTIONS = ("write_video", "video_fps", "video_quality", "video_subsampling", "video_in", "gpu_jpeg_parallel")
 _READERS = {}
 
 
@@ -173,7 +176,7 @@ def video_source(opt, device):
         return None
     from reface_amd.jpegdec import JpegDecoder
     from reface_amd.stream import VideoFrames
-    return VideoFrames(video_reader(opt), JpegDecoder(device))
+    return VideoFrames(video_reader(opt), JpegDecoder(device, parallel=opt.gpu_jpeg_parallel))
 
 
 def prepared_paths(opt):
@@ -442,6 +445,9 @@ def main(argv=None):
                          "is read (the crops of target_frames/ go through the dataset's host transforms)")
     if opt.gpu_png and opt.skip_save:
         print("inference_swap_video: --skip_save writes no files, so --gpu_png has nothing to encode")
+    if opt.gpu_jpeg_parallel and not opt.video_in:
+        raise SystemExit("inference_swap_video: --gpu_jpeg_parallel chooses a plan of the GPU JPEG decoder and needs --video_in; without it no JPEG "
+                         "frame is decoded")
     if opt.video_in:
         if not (opt.paste_back or opt.stream or opt.stream_keep):
             raise SystemExit("inference_swap_video: --video_in supplies the video's full frames for --paste_back or --stream; without either no frame "
