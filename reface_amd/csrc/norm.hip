@@ -20,8 +20,13 @@ constexpr int GN_THREADS = 256;
 template <typename T> struct gn_acc { typedef float type; };
 template <> struct gn_acc<float> { typedef double type; };   // fp32 (parity) path: fp64 partial sums throughout
 
-// thread t owns channel vectors {tv + q*TV}; pixel lanes stride over the chunk's pixels
-template <typename T>
+// thread t owns channel vectors {tv + q*TV}; pixel lanes stride over the chunk's pixels.
+// 16-bit storage: the fp32 running sums are SHIFTED, sum (x - K) and sum (x - K)^2 with K = the thread's first pixel of that channel, and
+// sum x = sum d + n K, sum x^2 = sum d^2 + 2 K sum d + n K^2 are formed once, in fp64.  Plain fp32 sums of x^2 lose the variance when |mean| is
+// large against the spread and a thread owns hundreds of pixels (512 pixels at mean / std = 64: a normalised value off by 5e-3); the shifted
+// squares are of the size of the spread itself.  Sums that were exact in fp32 stay exact.
+// NS = channel vectors per thread, as in gn_apply_kernel: one slot (C <= 256 * VEC) keeps sums and shifts in 24 registers instead of the 96 of four.
+template <typename T, int NS>
 __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const T* __restrict__ x, int HW, int C, int ldx, int nchunks,
                                                               double* __restrict__ partial) {
     typedef typename gn_acc<T>::type acc_t;
@@ -35,25 +40,49 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const T* __restric
     const int p0 = chunk * ppc, p1 = min(HW, p0 + ppc);
     const int cpg = C / 32;
 
-    acc_t s[GN_SLOTS][VEC], ss[GN_SLOTS][VEC];
+    constexpr bool SHIFTED = sizeof(T) == 2;
+    acc_t s[NS][VEC], ss[NS][VEC];
+    float k0[NS][VEC];
+    int npix = 0;
 #pragma unroll
-    for (int q = 0; q < GN_SLOTS; ++q)
+    for (int q = 0; q < NS; ++q)
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) s[q][e] = ss[q][e] = 0;
+        for (int e = 0; e < VEC; ++e) { s[q][e] = ss[q][e] = 0; k0[q][e] = 0.f; }
 
     if (pl < PL) {
-        for (int p = p0 + pl; p < p1; p += PL) {
+        int p = p0 + pl;
+        if (SHIFTED && p < p1) {                    // the thread's first pixel is the shift: its own d is 0
             const T* row = x + ((long long)b * HW + p) * ldx;
 #pragma unroll
-            for (int q = 0; q < GN_SLOTS; ++q) {
+            for (int q = 0; q < NS; ++q) {
+                const int v = tv + q * TV;
+                if (v < nvec) unpack16<T>(*(const u32x4_t*)(row + v * VEC), k0[q]);
+            }
+            npix = 1;
+            p += PL;
+        }
+        for (; p < p1; p += PL) {
+            const T* row = x + ((long long)b * HW + p) * ldx;
+#pragma unroll
+            for (int q = 0; q < NS; ++q) {
                 const int v = tv + q * TV;
                 if (v < nvec) {
                     float f[VEC];
                     unpack16<T>(*(const u32x4_t*)(row + v * VEC), f);
 #pragma unroll
-                    for (int e = 0; e < VEC; ++e) { s[q][e] += f[e]; ss[q][e] += (acc_t)f[e] * f[e]; }
+                    for (int e = 0; e < VEC; ++e) {
+                        if constexpr (SHIFTED) {
+                            const float d = f[e] - k0[q][e];
+                            s[q][e] += d;
+                            ss[q][e] += d * d;
+                        } else {
+                            s[q][e] += f[e];
+                            ss[q][e] += (acc_t)f[e] * f[e];
+                        }
+                    }
                 }
             }
+            ++npix;
         }
     }
     // deterministic two-stage reduction through LDS (no atomics): per-(pixel lane, channel) sums,
@@ -63,13 +92,19 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const T* __restric
     double* chq = chs + (size_t)PL * C;         // [PL][C]
     if (pl < PL) {
 #pragma unroll
-        for (int q = 0; q < GN_SLOTS; ++q) {
+        for (int q = 0; q < NS; ++q) {
             const int v = tv + q * TV;
             if (v < nvec) {
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
-                    chs[pl * C + v * VEC + e] = (double)s[q][e];
-                    chq[pl * C + v * VEC + e] = (double)ss[q][e];
+                    double sa = (double)s[q][e], sq = (double)ss[q][e];
+                    if constexpr (SHIFTED) {
+                        const double k = (double)k0[q][e], n = (double)npix;
+                        sq += (2.0 * sa + n * k) * k;
+                        sa += n * k;
+                    }
+                    chs[pl * C + v * VEC + e] = sa;
+                    chq[pl * C + v * VEC + e] = sq;
                 }
             }
         }
@@ -376,9 +411,14 @@ extern "C" int rf_groupnorm_stats(int dtype, const void* x, int B, int HW, int C
     const int nvec = C / vec, TV = nvec < GN_THREADS ? nvec : GN_THREADS, PL = GN_THREADS / TV;
     const size_t smem = (size_t)2 * PL * C * sizeof(double);
     RF_CHECK(smem <= 64 * 1024, "rf_groupnorm_stats: C=%d needs %zu B of LDS", C, smem);
-    if (dtype == RF_F32) hipLaunchKernelGGL(gn_stats_kernel<float>, grid, dim3(GN_THREADS), smem, (hipStream_t)stream, (const float*)x, HW, C, ldx, nchunks, partial);
-    else if (dtype == RF_F16) hipLaunchKernelGGL(gn_stats_kernel<f16_t>, grid, dim3(GN_THREADS), smem, (hipStream_t)stream, (const f16_t*)x, HW, C, ldx, nchunks, partial);
-    else hipLaunchKernelGGL(gn_stats_kernel<bf16_t>, grid, dim3(GN_THREADS), smem, (hipStream_t)stream, (const bf16_t*)x, HW, C, ldx, nchunks, partial);
+    const int ns = (nvec + GN_THREADS - 1) / GN_THREADS;      // channel vectors per thread
+#define GN_STATS_(T, NS_) hipLaunchKernelGGL((gn_stats_kernel<T, NS_>), grid, dim3(GN_THREADS), smem, (hipStream_t)stream, (const T*)x, HW, C, ldx, nchunks, partial)
+#define GN_STATS(T) { if (ns <= 1) GN_STATS_(T, 1); else if (ns <= 2) GN_STATS_(T, 2); else GN_STATS_(T, GN_SLOTS); }
+    if (dtype == RF_F32) GN_STATS(float)
+    else if (dtype == RF_F16) GN_STATS(f16_t)
+    else GN_STATS(bf16_t)
+#undef GN_STATS
+#undef GN_STATS_
     RF_LAUNCH_CHECK("rf_groupnorm_stats");
     return 0;
 }
