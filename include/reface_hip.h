@@ -469,6 +469,33 @@ int rf_paste_crop_u8(const float* x, int B, int h, int w, int S, void* out_u8, v
 int rf_paste_back_u8(const void* crops_u8, int B, int S, const double* coeffs, const void* frames_u8, int H, int W, int Cf, int64_t frame_stride,
                      void* out_u8, int Co, void* stream);
 /*
+ * The masked paste-back: the swapped crop is composited through a feathered alpha plane made of its face-parsing label map, so that only
+ * the region the model repaints (and a soft margin) replaces frame pixels.  Integer and PIL arithmetic throughout, byte for byte.
+ *   rf_paste_alpha_u8      : label maps u8 [B, Sl, Sl], lut256 u8 [256] (non-zero = the label is repainted) -> alpha u8 [B, S, S], S >= Sl:
+ *                              1. m = lut[label] ? 255 : 0;
+ *                              2. dilate: m[y, x] = max of m over |dy| <= dilate, |dx| <= dilate inside the map (0: identity);
+ *                              3. feather (skipped when feather = 0): `passes` times a horizontal, then a vertical 1-D box pass
+ *                                 out[i] = (sum_{|k| <= feather, 0 <= i + k < Sl} in[i + k] + feather) / (2 feather + 1), integer division:
+ *                                 positions outside the map count as 0, so alpha falls off towards the crop's border;
+ *                              4. Image.resize((S, S), BILINEAR) of the 8-bit plane (rf_paste_crop_u8's tap arithmetic on one channel);
+ *                                 S == Sl copies.
+ *                            dilate, feather in 0 .. 64, passes in 1 .. 3, else rc 1.  The passes are separable and go through `scratch_u8`,
+ *                            device memory of the caller's of scratch_bytes >= 2 * B * Sl * Sl bytes (two planes, read and written in turn).
+ *   rf_paste_back_alpha_u8 : rf_paste_back_u8 with alpha u8 [B, S, S] beside the crops: Image.transform((W, H), PERSPECTIVE, c, BILINEAR) of
+ *                            the RGBA image (crop, alpha) alpha-composited over the frame.  Coordinates and the inside test are
+ *                            rf_paste_back_u8's (outside or not finite: the frame pixel).  Inside, PIL warps the premultiplied image:
+ *                            the four taps are (MULDIV255(c, a), a), MULDIV255(x, y) = t = x y + 128, ((t >> 8) + t) >> 8, filtered by
+ *                            bilinear_filter32RGB on all four channels to (pr, pg, pb, pa); unless pa is 0 or 255, c = min(255, 255 pc / pa);
+ *                            then Image.alpha_composite over the frame pixel (dr, dg, db, da), da = 255 for 3-channel frames: pa = 0 keeps
+ *                            the frame pixel bit for bit; else blend = da (255 - pa), outa255 = 255 pa + blend, coef1 = pa 255 255 128 /
+ *                            outa255, coef2 = 255 128 - coef1, colour = SHIFT8(c coef1 + d coef2 + (0x80 << 7)) >> 7, alpha = SHIFT8(outa255
+ *                            + 0x80), SHIFT8(x) = ((x >> 8) + x) >> 8.  Strides, channel counts and the in-place rule are rf_paste_back_u8's.
+ */
+int rf_paste_alpha_u8(const void* labels_u8, int B, int Sl, const void* lut256_u8, int dilate, int feather, int passes, void* scratch_u8,
+                      int64_t scratch_bytes, void* alpha_u8, int S, void* stream);
+int rf_paste_back_alpha_u8(const void* crops_u8, const void* alpha_u8, int B, int S, const double* coeffs, const void* frames_u8, int H, int W, int Cf,
+                           int64_t frame_stride, void* out_u8, int Co, void* stream);
+/*
  * Face alignment (stage 1 of the swap callers, src/utils/alignmengt.py:crop_image): PIL's arithmetic, byte for byte (libImaging/Geometry.c,
  * Resample.c) -- the mirror image of the paste-back above.
  *   rf_align_quad_u8 : frames u8 [B, H, W, Cf] (frame b at frames + b * frame_stride bytes, Cf in {3, 4}: only R, G, B are read), coeffs fp64

@@ -1035,6 +1035,39 @@ def paste_back_u8(crops_u8, coeffs, frames_u8, out, name="paste_back_u8"):
                   (crops_u8, coeffs, frames_u8, out), name)
 
 
+def paste_alpha_u8(labels_u8, lut, out, scratch, dilate=8, feather=8, passes=2, name="paste_alpha_u8"):
+    """Label maps uint8 [B, Sl, Sl] and lut uint8 [256] (non-zero = the label is repainted) -> out uint8 [B, S, S], S >= Sl: the paste mask
+    (rf_paste_alpha_u8: 255 at the repainted labels, dilated by `dilate`, feathered by `passes` box blurs of radius `feather`, enlarged
+    by PIL's BILINEAR resize).  `scratch`: uint8, at least 2 * B * Sl * Sl elements."""
+    lib = _lib.load()
+    _require_gpu(labels_u8, lut, out, scratch)
+    B, Sl = labels_u8.shape[0], labels_u8.shape[1]
+    S = out.shape[1]
+    assert labels_u8.dtype == torch.uint8 and labels_u8.is_contiguous() and labels_u8.shape == (B, Sl, Sl)
+    assert lut.dtype == torch.uint8 and lut.is_contiguous() and lut.numel() == 256
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == (B, S, S)
+    assert scratch.dtype == torch.uint8 and scratch.is_contiguous()
+    return Launch(lib.rf_paste_alpha_u8, (_p(labels_u8), B, Sl, _p(lut), int(dilate), int(feather), int(passes), _p(scratch), scratch.numel(), _p(out), S),
+                  (labels_u8, lut, out, scratch), name)
+
+
+def paste_back_alpha_u8(crops_u8, alpha_u8, coeffs, frames_u8, out, name="paste_back_alpha_u8"):
+    """``paste_back_u8`` through the alpha planes alpha_u8 uint8 [B, S, S]: PIL's warp of the RGBA image (crop, alpha) and its
+    ``alpha_composite`` over the frames, byte for byte (rf_paste_back_alpha_u8).  Where the warped alpha is 0 the frame pixel stays."""
+    lib = _lib.load()
+    _require_gpu(crops_u8, alpha_u8, coeffs, frames_u8, out)
+    B, S = crops_u8.shape[0], crops_u8.shape[1]
+    _, H, W_, Cf = frames_u8.shape
+    assert crops_u8.dtype == torch.uint8 and crops_u8.is_contiguous() and crops_u8.shape == (B, S, S, 3)
+    assert alpha_u8.dtype == torch.uint8 and alpha_u8.is_contiguous() and alpha_u8.shape == (B, S, S)
+    assert coeffs.dtype == torch.float64 and coeffs.is_contiguous() and coeffs.shape == (B, 8)
+    assert frames_u8.dtype == torch.uint8 and frames_u8.shape[0] == B and frames_u8.stride(3) == 1 and frames_u8.stride(2) == Cf
+    assert frames_u8.stride(1) == W_ * Cf
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape[:3] == (B, H, W_)
+    return Launch(lib.rf_paste_back_alpha_u8, (_p(crops_u8), _p(alpha_u8), B, S, _p(coeffs), _p(frames_u8), H, W_, Cf, frames_u8.stride(0), _p(out),
+                                               out.shape[3]), (crops_u8, alpha_u8, coeffs, frames_u8, out), name)
+
+
 def align_quad_u8(frames_u8, coeffs, out, windows=None, name="align_quad_u8"):
     """PIL's Image.transform((S, S), QUAD, quad, BILINEAR) of frames uint8 [B, H, W, 3 | 4] (any frame stride; R, G, B are read) by the QUAD
     coefficients coeffs fp64 [B, 8] -> out uint8 [B, S, S, 3], byte for byte (rf_align_quad_u8).  `windows` int32 [B, 4] = (ox, oy, w, h)

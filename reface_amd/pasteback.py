@@ -9,6 +9,13 @@ reference), with the reference's PIL arithmetic reproduced byte for byte by two 
 The inverse transforms are stage 1's: ``alignment_coefficients(quad, 1024)`` of every frame's alignment quad (the reference's
 calc_alignment_coefficients(quad + 0.5, crop corners), :81-84).  Frame decoding and PNG encoding are host work on thread pools; the
 warp of a whole batch is one launch.
+
+With a ``PasteMask`` (not in the reference, which replaces the whole oriented square around the face) the crop is composited through a
+feathered alpha plane made of its face-parsing label map, so that only the labels the model repaints, and a soft margin, replace frame
+pixels -- still PIL's arithmetic byte for byte, now of ``crop.putalpha(alpha)`` instead of alpha 255:
+
+  alpha = 255 at the repainted labels, dilated, box-blurred, resized to 1024^2 (BILINEAR)                    rf_paste_alpha_u8
+  (crop, alpha) transformed as above (PIL warps the premultiplied image) and alpha-composited over the frame  rf_paste_back_alpha_u8
 """
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -78,11 +85,66 @@ def load_frames_device(decoder, frames_dir, sids):
     return decoder.decode([frame_item(frames_dir, sid) for sid in sids])
 
 
-def paste_on_device(result01, coeffs, frames, crop_size=CROP_SIZE, channels=4):
+class PasteMask:
+    """The alpha plane of the masked paste: 255 where the crop's label map has one of ``remove_labels`` (the labels the model repaints:
+    the dataset's ``remove_mask_tar_FFHQ``), grown by ``dilate`` label-map pixels, feathered by ``passes`` box blurs of radius ``feather``
+    (positions outside the map count as 0: alpha falls to 0 towards the crop's border, so the border of the square cannot show) and enlarged
+    to the crop (rf_paste_alpha_u8).  The defaults are a design choice for 512^2 label maps, not a measurement."""
+
+    def __init__(self, remove_labels, dilate=8, feather=8, passes=2):
+        self.dilate, self.feather, self.passes = int(dilate), int(feather), int(passes)
+        if not 0 <= self.dilate <= 64 or not 0 <= self.feather <= 64:
+            raise ValueError(f"dilate and feather are 0 .. 64 label-map pixels, got dilate={dilate} feather={feather}")
+        if not 1 <= self.passes <= 3:
+            raise ValueError(f"passes is 1 .. 3, got {passes}")
+        labels = np.asarray(list(remove_labels), dtype=np.int64)
+        if labels.size and (labels.min() < 0 or labels.max() > 255):
+            raise ValueError(f"labels are 0 .. 255, got {list(remove_labels)}")
+        self.lut_host = np.zeros(256, dtype=np.uint8)
+        self.lut_host[labels] = 1
+        self._lut = self._scratch = None
+
+    def alpha(self, labels_u8, S):
+        """Label maps uint8 [B, Sl, Sl] on the device -> alpha uint8 [B, S, S] on the device (S >= Sl)."""
+        if not torch.is_tensor(labels_u8) or labels_u8.dtype != torch.uint8 or labels_u8.dim() != 3 or labels_u8.shape[1] != labels_u8.shape[2]:
+            raise ValueError(f"label maps are a uint8 tensor [B, Sl, Sl], got {getattr(labels_u8, 'dtype', type(labels_u8))} "
+                             f"{tuple(getattr(labels_u8, 'shape', ()))}")
+        B, Sl = labels_u8.shape[0], labels_u8.shape[1]
+        if int(S) < Sl:
+            raise ValueError(f"the alpha plane is enlarged to the crop, never reduced: label maps of {Sl}, crops of {S}")
+        dev = labels_u8.device
+        if self._lut is None or self._lut.device != dev:
+            self._lut, self._scratch = torch.from_numpy(self.lut_host).to(dev), None
+        if self._scratch is None or self._scratch.numel() < 2 * B * Sl * Sl:          # (launches of one stream: the passes of the next call wait)
+            self._scratch = torch.empty(2 * B * Sl * Sl, dtype=torch.uint8, device=dev)
+        out = torch.empty((B, int(S), int(S)), dtype=torch.uint8, device=dev)
+        ops.paste_alpha_u8(labels_u8.contiguous(), self._lut, out, self._scratch, self.dilate, self.feather, self.passes)()
+        return out
+
+
+def load_labels(masks_dir, sid):
+    """Label map ``<masks_dir>/<int(sid)>.png`` (stage 1's ``<video>mask_frames``) as uint8 [Sl, Sl]."""
+    from PIL import Image
+    return np.asarray(Image.open(os.path.join(masks_dir, f"{int(sid)}.png")).convert("L"), dtype=np.uint8)
+
+
+def _labels_on(labels, B, dev):
+    """The batch's label maps (a uint8 tensor [B, Sl, Sl] or B arrays / tensors [Sl, Sl], host or device) as one device tensor."""
+    if labels is None:
+        raise ValueError("a masked paste needs the crops' label maps (labels=...)")
+    if not torch.is_tensor(labels):
+        labels = torch.stack([l if torch.is_tensor(l) else torch.from_numpy(np.ascontiguousarray(l)) for l in labels])
+    if labels.shape[0] != B:
+        raise ValueError(f"{labels.shape[0]} label maps for a batch of {B}")
+    return labels.to(dev)
+
+
+def paste_on_device(result01, coeffs, frames, crop_size=CROP_SIZE, channels=4, labels=None, mask=None):
     """The device half of stage 3 for frames that are on the device already: run_batch's fp32 [B, 3, h, w] result, the frames' inverse
     transforms (fp64 [B, 8], host) and B uint8 device tensors [H, W, 3 | 4] (sizes and channel counts may differ within the batch) ->
     (pasted frames: B uint8 device tensors [H, W, channels]; the enlarged crops uint8 [B, S, S, 3] on the device -- the bytes of
-    ``model_outputs/<id>.png``).  Nothing is copied to or from the host except the 8 coefficients per frame."""
+    ``model_outputs/<id>.png``).  Nothing is copied to or from the host except the 8 coefficients per frame.  With ``mask`` (a PasteMask)
+    the crops are pasted through the alpha planes of ``labels`` (their label maps, uint8 [B, Sl, Sl]); without it ``labels`` is not read."""
     B, S = result01.shape[0], int(crop_size)
     if len(frames) != B or len(coeffs) != B:
         raise ValueError(f"{len(frames)} frames and {len(coeffs)} transforms for a batch of {B}")
@@ -90,6 +152,7 @@ def paste_on_device(result01, coeffs, frames, crop_size=CROP_SIZE, channels=4):
     crops = torch.empty((B, S, S, 3), dtype=torch.uint8, device=dev)
     ops.paste_crop_u8(result01.float().contiguous(), crops)()
     co = torch.from_numpy(np.ascontiguousarray(coeffs, dtype=np.float64).reshape(B, 8)).to(dev)
+    alpha = mask.alpha(_labels_on(labels, B, dev), S) if mask is not None else None
     out = [None] * B
     groups = {}
     for i, f in enumerate(frames):          # one launch per frame size (all frames of a video share one)
@@ -99,7 +162,11 @@ def paste_on_device(result01, coeffs, frames, crop_size=CROP_SIZE, channels=4):
         sel = torch.tensor(members, device=dev)
         fr = torch.stack([frames[i] for i in members])
         o = torch.empty(fr.shape[:3] + (int(channels),), dtype=torch.uint8, device=dev)
-        ops.paste_back_u8(crops if whole else crops.index_select(0, sel).contiguous(), co if whole else co.index_select(0, sel).contiguous(), fr, o)()
+        cr, cs = (crops, co) if whole else (crops.index_select(0, sel).contiguous(), co.index_select(0, sel).contiguous())
+        if alpha is None:
+            ops.paste_back_u8(cr, cs, fr, o)()
+        else:
+            ops.paste_back_alpha_u8(cr, alpha if whole else alpha.index_select(0, sel).contiguous(), cs, fr, o)()
         for k, i in enumerate(members):
             out[i] = o[k]
     return out, crops
@@ -107,17 +174,36 @@ def paste_on_device(result01, coeffs, frames, crop_size=CROP_SIZE, channels=4):
 
 class PasteBack:
     """The device half of stage 3 for one video: ``prefetch(ids)`` starts decoding the frames of a batch on a thread pool; ``paste(result01,
-    ids)`` turns run_batch's fp32 [B, 3, h, w] result into the pasted frames (uint8 [H, W, channels] host arrays, one per id)."""
+    ids)`` turns run_batch's fp32 [B, 3, h, w] result into the pasted frames (uint8 [H, W, channels] host arrays, one per id).  With ``mask``
+    (a PasteMask) the paste goes through the crops' label maps: those handed to ``paste`` / ``paste_device`` (``labels=``), else the files
+    ``<masks_dir>/<int(id)>.png``, which ``prefetch`` then also reads on its pool."""
 
-    def __init__(self, frames_dir, inv_transforms, crop_size=CROP_SIZE, channels=4, threads=None):
+    def __init__(self, frames_dir, inv_transforms, crop_size=CROP_SIZE, channels=4, threads=None, mask=None, masks_dir=None):
         self.frames_dir, self.S, self.channels = frames_dir, int(crop_size), int(channels)
+        self.mask, self.masks_dir, self._labels = mask, masks_dir, {}
+        if mask is not None and not isinstance(mask, PasteMask):
+            raise TypeError(f"mask is a PasteMask, got {type(mask).__name__}")
         self.coeffs = load_inv_transforms(inv_transforms) if isinstance(inv_transforms, str) else np.asarray(inv_transforms, dtype=np.float64)
         self.pool = ThreadPoolExecutor(max_workers=threads or max(2, min(8, available_cpus() // 2)))
 
     def prefetch(self, ids):
+        if self.mask is not None and self.masks_dir is not None:          # (paste / paste_device take them from here)
+            for sid in ids:
+                self._labels[int(sid)] = self.pool.submit(load_labels, self.masks_dir, sid)
         return [self.pool.submit(load_frame, self.frames_dir, sid) for sid in ids]
 
-    def paste(self, result01, ids, frames=None):
+    def _batch_labels(self, idx, labels, dev):
+        """The label maps of the masked paste of frames `idx` on the device (None without a mask): `labels`, else the prefetched files."""
+        if self.mask is None:
+            return None
+        if labels is None:
+            if self.masks_dir is None:
+                raise ValueError("a masked paste needs the crops' label maps: labels=..., or PasteBack(masks_dir=...)")
+            futures = [self._labels.pop(i, None) for i in idx]
+            labels = [f.result() if f is not None else load_labels(self.masks_dir, i) for f, i in zip(futures, idx)]
+        return _labels_on(labels, len(idx), dev)
+
+    def paste(self, result01, ids, frames=None, labels=None):
         ids = list(ids)
         if len(ids) != result01.shape[0]:
             raise ValueError(f"{len(ids)} ids for a batch of {result01.shape[0]}")
@@ -131,6 +217,8 @@ class PasteBack:
         crops = torch.empty((len(ids), self.S, self.S, 3), dtype=torch.uint8, device=dev)
         ops.paste_crop_u8(x, crops)()
         coeffs = torch.from_numpy(self.coeffs[idx]).to(dev)
+        labels = self._batch_labels(idx, labels, dev)
+        alpha = self.mask.alpha(labels, self.S) if labels is not None else None
         out = [None] * len(ids)
         groups = {}
         for i, f in enumerate(frames):          # one launch per frame size (all frames of a video share one)
@@ -139,13 +227,17 @@ class PasteBack:
             sel = torch.tensor(members, device=dev)
             fr = torch.from_numpy(np.stack([frames[i] for i in members])).pin_memory().to(dev, non_blocking=True)
             o = torch.empty(fr.shape[:3] + (self.channels,), dtype=torch.uint8, device=dev)
-            ops.paste_back_u8(crops.index_select(0, sel).contiguous(), coeffs.index_select(0, sel).contiguous(), fr, o)()
+            if alpha is None:
+                ops.paste_back_u8(crops.index_select(0, sel).contiguous(), coeffs.index_select(0, sel).contiguous(), fr, o)()
+            else:
+                ops.paste_back_alpha_u8(crops.index_select(0, sel).contiguous(), alpha.index_select(0, sel).contiguous(),
+                                        coeffs.index_select(0, sel).contiguous(), fr, o)()
             host = o.cpu().numpy()
             for k, i in enumerate(members):
                 out[i] = host[k]
         return out
 
-    def paste_device(self, result01, ids, frames):
+    def paste_device(self, result01, ids, frames, labels=None):
         """``paste`` for frames that are on the device already (B uint8 device tensors [H, W, 3 | 4]): the pasted frames stay there too
         (B uint8 device tensors [H, W, channels]); the same bytes as ``paste``."""
         ids = list(ids)
@@ -155,7 +247,8 @@ class PasteBack:
         bad = [s for s, i in zip(ids, idx) if not 0 <= i < len(self.coeffs)]
         if bad:
             raise IndexError(f"frames {bad} have no inverse transform ({len(self.coeffs)} in the file)")
-        return paste_on_device(result01, self.coeffs[idx], frames, crop_size=self.S, channels=self.channels)[0]
+        return paste_on_device(result01, self.coeffs[idx], frames, crop_size=self.S, channels=self.channels,
+                               labels=self._batch_labels(idx, labels, result01.device), mask=self.mask)[0]
 
     def close(self):
         self.pool.shutdown(wait=True)

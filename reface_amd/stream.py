@@ -6,6 +6,8 @@ and stays on the device until its pasted version is downloaded.
                                       -> rf_video_prep_u8       target, keep-mask, masked target fp32       (the dataset's __getitem__)
   SwapRunner.run_batch                -> rf_paste_crop_u8       swapped crops u8 [B, 1024, 1024, 3]
                                       -> rf_paste_back_u8       pasted frames u8 [H, W, 4]
+  (with a paste mask, instead)        -> rf_paste_alpha_u8      alpha u8 [B, 1024, 1024] of the batch's label maps
+                                      -> rf_paste_back_alpha_u8 pasted frames u8 [H, W, 4]
 
 The staged route passes every arrow through PNG files (``<video>cropped_face/``, ``<video>mask_frames/``, ``model_outputs/``) and decodes
 every frame twice; each tensor here is the one the staged route would have decoded from its file, bit for bit: the crops and label maps come
@@ -98,7 +100,9 @@ class VideoStream:
     """One video's device chain.  ``landmarks`` fp64 [N, 68, 2] of ALL frames (a non-finite row = no face: the frame uses the crop, label
     map and transform of the last frame that had one, across batches; a first frame without a face raises, here, before anything touches the
     GPU).  ``remove_labels``: the label list of the dataset's keep-mask (``remove_mask_tar_FFHQ``, or [2, 3, 5, 6, 7] without
-    ``gray_outer_mask``).  ``parser``: a FaceParser (made on first use from ``seg_ckpt`` otherwise).
+    ``gray_outer_mask``).  ``parser``: a FaceParser (made on first use from ``seg_ckpt`` otherwise).  ``paste_mask``: a
+    ``pasteback.PasteMask``; ``paste`` then composites every crop through the alpha plane of its label map (``state["labels"]``: a frame
+    that repeats an earlier face uses that face's labels) instead of replacing the whole quad.
 
       prepare(frames, ids)  -> (test_batch, {"inpaint_image", "inpaint_mask"}, state)    frames: stacked uint8 tensor or list, host or device
       paste(x_img, state)   -> (pasted frames: B uint8 device tensors [H, W, channels], swapped crops uint8 [B, S, S, 3] on the device)
@@ -106,7 +110,7 @@ class VideoStream:
     ``state`` holds the batch's frames on the device, their indices and inverse transforms, and the crops / label maps (for --stream_keep)."""
 
     def __init__(self, landmarks, remove_labels, *, seg_ckpt=None, seg12=True, parser=None, image_size=512, crop_size=CROP_SIZE, channels=4,
-                 device="cuda"):
+                 device="cuda", paste_mask=None):
         lm = np.asarray(landmarks, dtype=np.float64)
         self.src_of = fill_missing(lm)
         self.quads = {i: quad_from_landmarks(lm[i])[3] for i in sorted(set(self.src_of))}
@@ -115,6 +119,7 @@ class VideoStream:
         self.S, self.size, self.channels, self.seg12 = int(crop_size), int(image_size), int(channels), bool(seg12)
         self.device, self.seg_ckpt, self.parser = torch.device(device), seg_ckpt, parser
         self.lut_host = keep_lut(remove_labels)
+        self.paste_mask = paste_mask
         self.aligner = self.lut = self.taps = None
         self.last = None          # (frame index, crop u8 [1, S, S, 3], labels u8 [1, S/2, S/2]) of the last frame that had a face
 
@@ -193,7 +198,10 @@ class VideoStream:
 
     @torch.no_grad()
     def paste(self, x_img, state):
-        return paste_on_device(x_img, state["inv_transforms"], state["frames"], crop_size=self.S, channels=self.channels)
+        if self.paste_mask is None:
+            return paste_on_device(x_img, state["inv_transforms"], state["frames"], crop_size=self.S, channels=self.channels)
+        return paste_on_device(x_img, state["inv_transforms"], state["frames"], crop_size=self.S, channels=self.channels, labels=state["labels"],
+                               mask=self.paste_mask)
 
 
 def stream_paths(base_dir, target_video, outdir):

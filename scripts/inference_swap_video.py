@@ -51,6 +51,15 @@ The reference's H.264 mp4 + audio mux of stage 3 is not built (no video encoder 
 writes -- instead of ``<Base_dir>/<video>/<i>.png``: frame i is the file's i-th frame, decoded on the GPU (reface_amd/jpegdec.py: exactly
 PIL's array) as RGB; ``--landmarks`` index its frames (and are required: dlib reads image files), ``drop_last`` and the ids are unchanged,
 and ``--write_video`` without ``--video_fps`` takes the input's rate.
+
+``--paste_mask`` (with ``--paste_back`` or ``--stream``; not in the reference) pastes every swapped crop through a feathered mask instead of
+replacing the whole oriented square around the face: alpha is 255 where the crop's face-parsing label map (``<video>mask_frames/<i>.png``,
+or the stream's label maps on the device) has a label the model repaints (``remove_mask_tar_FFHQ``, or [2, 3, 5, 6, 7]), grown by
+``--paste_dilate`` pixels of the 512^2 label map (default 8), softened by two box blurs of radius ``--paste_feather`` (default 8) that fall
+to 0 towards the crop's border, and enlarged to 1024^2; the crop with that alpha is warped and ``alpha_composite``-d over the frame with
+PIL's arithmetic, byte for byte (rf_paste_alpha_u8, rf_paste_back_alpha_u8).  Where the mask has no support the written frame is the input
+frame bit for bit.  Only ``results/<id>.png`` and the video change; ``model_outputs/`` and every other file are what they are without the
+flag.  The defaults are a design choice: no trained checkpoint was available, so the effect on image quality is not measured.
 """
 import argparse
 import os
@@ -148,6 +157,13 @@ def build_parser():
     p.add_argument("--gpu_jpeg_parallel", action="store_true", help="--video_in: frames without restart markers (an MJPG file of another writer) "
                    "are decoded by one lane per sub-sequence of the scan (the self-synchronising plan of reface_amd/jpegdec.py) instead of one lane "
                    "per frame; the frames are the same")
+    p.add_argument("--paste_mask", action="store_true", help="--paste_back / --stream: composite every swapped crop through a feathered alpha plane "
+                   "made of its face-parsing label map (the labels the model repaints, remove_mask_tar_FFHQ) instead of replacing the whole "
+                   "square around the face; where the mask has no support the frame's pixels stay bit for bit")
+    p.add_argument("--paste_dilate", type=int, default=8, metavar="N", help="--paste_mask: grow the repainted region by N pixels of the 512^2 "
+                   "label map before feathering, 0 .. 64 (default 8)")
+    p.add_argument("--paste_feather", type=int, default=8, metavar="N", help="--paste_mask: radius of the two box blurs that soften the mask's "
+                   "edge, in pixels of the label map, 0 .. 64 (default 8; 0 = a hard edge)")
     p.add_argument("--video_quality", type=int, default=90, help="--write_video: libjpeg quality, 1 .. 100 (default 90)")
     p.add_argument("--video_subsampling", type=str, choices=["420", "444"], default="420", help="--write_video: chroma subsampling (default 420)")
     return p
@@ -301,7 +317,7 @@ def run_stream(opt):
     config = rcfg.load(opt.config)
     test_args = dict(config.data.params.test.params)
     remove = test_args["remove_mask_tar_FFHQ"] if test_args["gray_outer_mask"] else [2, 3, 5, 6, 7]
-    vs = VideoStream(lm, remove, seg_ckpt=opt.faceParsing_ckpt, seg12=opt.seg12)          # host fp64 only: quads and inverse transforms of EVERY frame
+    vs = VideoStream(lm, remove, seg_ckpt=opt.faceParsing_ckpt, seg12=opt.seg12, paste_mask=make_paste_mask(opt, test_args))          # host fp64 only: quads and inverse transforms of EVERY frame
     pp, sp = prepared_paths(opt), pasteback_paths(opt)
     np.save(sp["inv_transforms"], vs.inv_transforms)
     torch.manual_seed(opt.seed)
@@ -382,8 +398,23 @@ def run_stream(opt):
           f"transforms of all {len(paths)} frames to {sp['inv_transforms']}; "
           + (f"crops, label maps and swapped crops of the swapped frames kept in {', '.join(keep.values())}" if keep else
              "no crops, label maps or model_outputs files were written (--stream_keep writes them)")
-          + (video_clause(opt, video_files) if video is not None else " (the mp4 + audio mux of the reference's stage 3 is not built)."))
+          + mask_clause(opt) + (video_clause(opt, video_files) if video is not None else " (the mp4 + audio mux of the reference's stage 3 is not built)."))
     return n_done
+
+
+def make_paste_mask(opt, test_args):
+    """--paste_mask: the PasteMask of the labels the dataset's keep-mask cuts out of the target (None without the flag)."""
+    if not opt.paste_mask:
+        return None
+    from reface_amd.pasteback import PasteMask
+    remove = test_args["remove_mask_tar_FFHQ"] if test_args["gray_outer_mask"] else [2, 3, 5, 6, 7]
+    return PasteMask(remove, dilate=opt.paste_dilate, feather=opt.paste_feather)
+
+
+def mask_clause(opt):
+    """The closing line's account of --paste_mask."""
+    return (f"; pasted through the feathered mask of the repainted labels (--paste_mask: dilate {opt.paste_dilate}, feather {opt.paste_feather}, "
+            "2 passes, at the label map's size)") if opt.paste_mask else ""
 
 
 def make_png_decoder(opt, device):
@@ -445,6 +476,14 @@ def main(argv=None):
                          "is read (the crops of target_frames/ go through the dataset's host transforms)")
     if opt.gpu_png and opt.skip_save:
         print("inference_swap_video: --skip_save writes no files, so --gpu_png has nothing to encode")
+    if opt.paste_mask and not (opt.paste_back or opt.stream or opt.stream_keep):
+        raise SystemExit("inference_swap_video: --paste_mask composites the pasted frames of results/ through the crops' label maps and needs "
+                         "--paste_back or --stream (model_outputs/ holds crops, not frames)")
+    for flag, value in (("--paste_dilate", opt.paste_dilate), ("--paste_feather", opt.paste_feather)):
+        if not opt.paste_mask and any(a == flag or a.startswith(flag + "=") for a in (sys.argv[1:] if argv is None else argv)):
+            raise SystemExit(f"inference_swap_video: {flag} shapes the mask of --paste_mask and needs it; without it every pixel of the quad is replaced")
+        if not 0 <= value <= 64:
+            raise SystemExit(f"inference_swap_video: {flag} is 0 .. 64 pixels of the label map, got {value}")
     if opt.gpu_jpeg_parallel and not opt.video_in:
         raise SystemExit("inference_swap_video: --gpu_jpeg_parallel chooses a plan of the GPU JPEG decoder and needs --video_in; without it no JPEG "
                          "frame is decoded")
@@ -520,7 +559,8 @@ def main(argv=None):
     if opt.paste_back and not opt.skip_save:
         from reface_amd.pasteback import PasteBack, PngWriter
         sp = pasteback_paths(opt)
-        paster, writer = PasteBack(sp["video_frames"], sp["inv_transforms"]), PngWriter(png_encoder=make_png_encoder(opt, device))
+        paster = PasteBack(sp["video_frames"], sp["inv_transforms"], mask=make_paste_mask(opt, test_args), masks_dir=pp["masks"])
+        writer = PngWriter(png_encoder=make_png_encoder(opt, device))
     video = make_video(opt, device) if paster is not None else None
     source = video_source(opt, device) if paster is not None else None
     decoder = (source.decoder if source is not None else make_png_decoder(opt, device)) if paster is not None else None
@@ -577,7 +617,7 @@ def main(argv=None):
         if decoder is not None:
             print("inference_swap_video --" + decoder_line(opt, decoder))
         print(f"Swapped crops of {n_done} frames are in {model_out}; {n_pasted} pasted frames are in {os.path.join(opt.outdir, 'results')}"
-              + (video_clause(opt, video_files) if video is not None else " (the mp4 + audio mux of the reference's stage 3 is not built)."))
+              + mask_clause(opt) + (video_clause(opt, video_files) if video is not None else " (the mp4 + audio mux of the reference's stage 3 is not built)."))
     else:
         print(f"Swapped crops of {n_done} frames are in {model_out}; the reference's stage 3 (paste back with the inverse alignment of every frame, "
               f"mp4 + audio) takes them from there (--paste_back pastes them back on the GPU).")
