@@ -43,6 +43,9 @@ def build_parser():
     p.add_argument("--gpu_jpeg_parallel", action="store_true",
                    help="(addition) with --gpu_jpeg_decode: files without restart markers are decoded by one lane per sub-sequence of the scan "
                         "(the self-synchronising plan of reface_amd/jpegdec.py) instead of one lane per file; the values are the same")
+    p.add_argument("--gpu_png_parallel", action="store_true",
+                   help="(addition) with --gpu_png_decode: PNG files that --gpu_png did not write are inflated by one wave per dynamic Huffman block "
+                        "(the blocks plan of reface_amd/pngdec.py) instead of one wave per file; the values are the same")
     p.add_argument("--json", type=str, default=None,
                    help="(addition) write Expression_value, distances, labels, expression coefficients, image count and images/s (decode to score; engine "
                         "construction excluded) to this file")
@@ -53,6 +56,9 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.gpu_jpeg_parallel and not args.gpu_jpeg_decode:
         raise SystemExit("expression_compare_face_recon: --gpu_jpeg_parallel chooses a plan of the GPU JPEG decoder and needs --gpu_jpeg_decode; without it no file "
+                         "is decoded on the GPU")
+    if args.gpu_png_parallel and not args.gpu_png_decode:
+        raise SystemExit("expression_compare_face_recon: --gpu_png_parallel chooses a plan of the GPU PNG decoder and needs --gpu_png_decode; without it no file "
                          "is decoded on the GPU")
     import torch
     from reface_amd.exprscore import NPZ_REFUSED, ExprScorer, list_images_sorted, load_recon_state, parse_labels_first
@@ -75,10 +81,10 @@ def main(argv=None):
     scorer = ExprScorer(state, batch=args.batch_size, device=device)
     if args.gpu_jpeg_decode:          # one decoder behind both flags: every file goes by its signature
         from reface_amd.jpegdec import FileDecoder
-        scorer.png_decoder = FileDecoder(device, png=args.gpu_png_decode, jpeg=True, jpeg_parallel=args.gpu_jpeg_parallel)
+        scorer.png_decoder = FileDecoder(device, png=args.gpu_png_decode, jpeg=True, jpeg_parallel=args.gpu_jpeg_parallel, png_parallel=args.gpu_png_parallel)
     elif args.gpu_png_decode:
         from reface_amd.pngdec import PngDecoder
-        scorer.png_decoder = PngDecoder(device)
+        scorer.png_decoder = PngDecoder(device, parallel=args.gpu_png_parallel)
     r = scorer.score_folders(args.path, num_workers=num_workers)
     print("Expression_value: ", r["expression_value"])
     if args.print_sim:

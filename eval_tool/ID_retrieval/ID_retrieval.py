@@ -50,6 +50,9 @@ def build_parser():
     p.add_argument("--gpu_jpeg_parallel", action="store_true",
                    help="(addition) with --gpu_jpeg_decode: files without restart markers are decoded by one lane per sub-sequence of the scan "
                         "(the self-synchronising plan of reface_amd/jpegdec.py) instead of one lane per file; the values are the same")
+    p.add_argument("--gpu_png_parallel", action="store_true",
+                   help="(addition) with --gpu_png_decode: PNG files that --gpu_png did not write are inflated by one wave per dynamic Huffman block "
+                        "(the blocks plan of reface_amd/pngdec.py) instead of one wave per file; the values are the same")
     p.add_argument("--json", type=str, default=None,
                    help="(addition) write top1, top5, mean, similarities, labels, image count and images/s (decode to scores; engine construction excluded) to this file")
     p.add_argument("--precision", type=str, choices=["full", "bf16"], default="full", help="(addition) precision of the ArcFace engine")
@@ -60,6 +63,9 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.gpu_jpeg_parallel and not args.gpu_jpeg_decode:
         raise SystemExit("ID_retrieval: --gpu_jpeg_parallel chooses a plan of the GPU JPEG decoder and needs --gpu_jpeg_decode; without it no file "
+                         "is decoded on the GPU")
+    if args.gpu_png_parallel and not args.gpu_png_decode:
+        raise SystemExit("ID_retrieval: --gpu_png_parallel chooses a plan of the GPU PNG decoder and needs --gpu_png_decode; without it no file "
                          "is decoded on the GPU")
     if not args.arcface:
         raise SystemExit("ID_retrieval: --arcface True is required (the reference defines no other identity model)")
@@ -76,10 +82,10 @@ def main(argv=None):
     scorer = IDScorer(load_arcface_state(args.arcface_ckpt), precision=args.precision, batch=args.batch_size, device=device)
     if args.gpu_jpeg_decode:          # one decoder behind both flags: every file goes by its signature
         from reface_amd.jpegdec import FileDecoder
-        scorer.png_decoder = FileDecoder(device, png=args.gpu_png_decode, jpeg=True, jpeg_parallel=args.gpu_jpeg_parallel)
+        scorer.png_decoder = FileDecoder(device, png=args.gpu_png_decode, jpeg=True, jpeg_parallel=args.gpu_jpeg_parallel, png_parallel=args.gpu_png_parallel)
     elif args.gpu_png_decode:
         from reface_amd.pngdec import PngDecoder
-        scorer.png_decoder = PngDecoder(device)
+        scorer.png_decoder = PngDecoder(device, parallel=args.gpu_png_parallel)
     r = scorer.score_folders(args.path, dataset=args.dataset, num_workers=num_workers)
     print("Top-1 accuracy: {:.2f}%".format(r["top1"] * 100))
     print("Top-5 accuracy: {:.2f}%".format(r["top5"] * 100))

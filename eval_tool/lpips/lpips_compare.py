@@ -42,6 +42,9 @@ def build_parser():
     p.add_argument("--gpu_jpeg_parallel", action="store_true",
                    help="(addition) with --gpu_jpeg_decode: files without restart markers are decoded by one lane per sub-sequence of the scan "
                         "(the self-synchronising plan of reface_amd/jpegdec.py) instead of one lane per file; the values are the same")
+    p.add_argument("--gpu_png_parallel", action="store_true",
+                   help="(addition) with --gpu_png_decode: PNG files that --gpu_png did not write are inflated by one wave per dynamic Huffman block "
+                        "(the blocks plan of reface_amd/pngdec.py) instead of one wave per file; the values are the same")
     p.add_argument("--json", type=str, default=None,
                    help="write LPIPS_value, distances, labels, image count and images/s (decode to score; engine construction excluded) to this file")
     return p
@@ -51,6 +54,9 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.gpu_jpeg_parallel and not args.gpu_jpeg_decode:
         raise SystemExit("lpips_compare: --gpu_jpeg_parallel chooses a plan of the GPU JPEG decoder and needs --gpu_jpeg_decode; without it no file "
+                         "is decoded on the GPU")
+    if args.gpu_png_parallel and not args.gpu_png_decode:
+        raise SystemExit("lpips_compare: --gpu_png_parallel chooses a plan of the GPU PNG decoder and needs --gpu_png_decode; without it no file "
                          "is decoded on the GPU")
     import torch
     from reface_amd.idscore import list_images
@@ -74,10 +80,10 @@ def main(argv=None):
     scorer = LPIPSScorer(state, net=args.net, batch=args.batch_size, device=device)
     if args.gpu_jpeg_decode:          # one decoder behind both flags: every file goes by its signature
         from reface_amd.jpegdec import FileDecoder
-        scorer.png_decoder = FileDecoder(device, png=args.gpu_png_decode, jpeg=True, jpeg_parallel=args.gpu_jpeg_parallel)
+        scorer.png_decoder = FileDecoder(device, png=args.gpu_png_decode, jpeg=True, jpeg_parallel=args.gpu_jpeg_parallel, png_parallel=args.gpu_png_parallel)
     elif args.gpu_png_decode:
         from reface_amd.pngdec import PngDecoder
-        scorer.png_decoder = PngDecoder(device)
+        scorer.png_decoder = PngDecoder(device, parallel=args.gpu_png_parallel)
     try:
         r = scorer.score_folders(args.path, num_workers=num_workers)
     except ValueError as e:          # a result whose size differs from its target's, an image too small for the net

@@ -682,7 +682,8 @@ int rf_png_pack(const void* slots_u8, const int* seg_bytes, const uint32_t* seg_
  *   7 out_c                  channels written: bpp, or 1 | 3 from grey (+ alpha: dropped; the sample is replicated), or 3 from RGBA
  *   8 pix_off, 9 row_stride  the image's pixels at pix + pix_off, row y at + y * row_stride bytes
  *   10 cand_begin, 11 cand_count   the file's candidate piece starts: cand[cand_begin ...]; 0, or the stream start (offset 2) and the rest
- * status is int32 [B, 2]: the error code (0 = none; the codes of csrc/png_inflate.h) and the inflate plan taken (0 serial, 1 segments).
+ * status is int32 [B, 2]: the error code (0 = none; the codes of csrc/png_inflate.h) and the inflate plan taken (0 serial, 1 segments,
+ * 2 blocks).
  *   rf_png_inflate     : zlib streams -> filtered streams.  Every read is bounded by comp_len, every write by expect, every distance by the
  *                        bytes produced so far; a damaged stream leaves an error code.  Serial plan: one wave per stream, the Huffman
  *                        symbols walked on wave-uniform values, the 32 KiB window and the tables in LDS, matches and stored blocks copied
@@ -697,10 +698,30 @@ int rf_png_pack(const void* slots_u8, const int* seg_bytes, const uint32_t* seg_
  *   rf_png_unfilter_u8 : filtered streams -> pixels (None / Sub / Up / Average / Paeth undone in exact integer arithmetic), one wave per
  *                        image, W <= 8192, H <= 2^20.  Files whose error code is set are skipped; a filter byte above 4 sets code 11.  status must
  *                        have been written by rf_png_inflate (or zeroed).
+ *   rf_png_inflate_blocks : rf_png_inflate's sequence with the blocks plan (csrc/png_blocks.h) in front of the serial kernel, for the files
+ *                        the caller names eligible (an opt-in: the plan only accepts a file; whatever it does not accept is decoded, and
+ *                        its error code set, by the serial kernel behind it).  blk is int32 [3 B + nslot] (blk_host = the same words on the
+ *                        host): per file the capacity in candidate slots (0 = not eligible; else >= 2, and comp_len < 2^28), its first
+ *                        slot (the files' slots follow each other) and the first word of its candidate bitmap ((comp_len + 3) / 4 words
+ *                        per eligible file, following each other); then the file of every slot.  bitmap is uint32 [bitmap_words], work
+ *                        int32 [work_words >= 4 B + 11 nslot], marks uint16 [marks_count >= filt_bytes]: 2 bytes per output byte, at the
+ *                        file's filt_off.  Five launches, no host round trip: search (one lane per bit offset of an eligible stream tests
+ *                        whether a dynamic block header the serial plan would accept starts there; the bit behind the zlib header is
+ *                        candidate 0 whatever stands there; a file with more hits than slots is not accepted), count (one wave per
+ *                        candidate walks whole blocks to the next block boundary that is a candidate), chain (one thread per file, from
+ *                        candidate 0 along the end bits: every chunk usable, the last one final, the total = expect, at least 2 chunks),
+ *                        decode (one wave per chain chunk writes 16-bit symbols: a byte, or 256 + j = byte j of the 32 KiB in front of
+ *                        the chunk), resolve (one workgroup per file, chunk by chunk; a marker in front of the stream's first byte or an
+ *                        Adler-32 other than the trailer's rejects the file).  Files the segmented plan accepted are skipped.  After the
+ *                        call work[4 f .. 4 f + 1] = the dynamic headers found in file f (candidate 0 not counted) and its chain length.
  */
 #define RF_PNGDEC_DESC 12
 int rf_png_inflate(const void* comp_u8, int64_t comp_bytes, const int64_t* desc_host, const int64_t* desc, int B, void* filt_u8, int64_t filt_bytes,
                    const int* cand_host, const int* cand, int ncand, void* slots_u8, int* pieces, int* status, void* stream);
+int rf_png_inflate_blocks(const void* comp_u8, int64_t comp_bytes, const int64_t* desc_host, const int64_t* desc, int B, void* filt_u8, int64_t filt_bytes,
+                          const int* cand_host, const int* cand, int ncand, void* slots_u8, int* pieces, int* status, const int* blk_host, const int* blk,
+                          int nslot, void* bitmap_u32, int64_t bitmap_words, int* work, int64_t work_words, void* marks_u16, int64_t marks_count,
+                          void* stream);
 int rf_png_unfilter_u8(const void* filt_u8, int64_t filt_bytes, const int64_t* desc_host, const int64_t* desc, int B, void* pix_u8, int64_t pix_bytes,
                        int* status, void* stream);
 

@@ -28,7 +28,7 @@ UNIT_DEPS = {"gemm_f16.hip": [os.path.join(CSRC, "gemm.hip")], "pasteback.hip": 
              "idscore.hip": [os.path.join(CSRC, "cv_u8.h")], "expr.hip": [os.path.join(CSRC, "pil_u8.h")],
              "fid.hip": [os.path.join(CSRC, "pil_u8.h")],
              # png_inflate.h: the zlib decoder core, compiled by hipcc here and by a host compiler into tests/pngdec_host_main.cpp
-             "pngdec.hip": [os.path.join(CSRC, "png_inflate.h")],
+             "pngdec.hip": [os.path.join(CSRC, "png_inflate.h"), os.path.join(CSRC, "png_blocks.h")],
              # jpeg_decode.h: the JPEG entropy-decoder core, compiled by hipcc here and by a host compiler into tests/jpegdec_host_main.cpp
              "jpegdec.hip": [os.path.join(CSRC, "jpeg_decode.h"), os.path.join(CSRC, "jpeg_sync.h")]}
 

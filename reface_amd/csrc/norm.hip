@@ -392,7 +392,7 @@ extern "C" const char* rf_last_error(void) { return rf::g_err; }
 // 104: rf_conv_gemm_plan3 (the whole launch plan of rf_conv_gemm as a host-only query)
 // 105: rf_attention_plan (the launch plan of rf_attention as a host-only query)
 // 106: rf_dpm_update (the DPM-Solver++ multistep update)
-extern "C" int rf_version(void) { return 110; }
+extern "C" int rf_version(void) { return 111; }
 
 static int gn_check(const char* name, int dtype, int C, int ldx, int nchunks) {
     const int vec = dtype == RF_F32 ? 4 : 8;

@@ -92,6 +92,19 @@ template <class Src> struct BitReader {
         nbits = 0;
         pos = p;
     }
+    // The blocks plan (png_blocks.h) reads from a bit offset: bit < 2^31.  False where the offset lies behind the stream.
+    RF_HD bool seek_bit(uint32_t bit) {
+        const uint32_t p = bit >> 3;
+        if (p > src.size()) {
+            seek(src.size());
+            return false;
+        }
+        seek(p);
+        if (!need((int)(bit & 7))) return false;
+        take((int)(bit & 7));
+        return true;
+    }
+    RF_HD uint32_t bitpos() const { return 8u * pos - (uint32_t)nbits; }          // the next unread bit (pos < 2^28 on that plan)
 };
 
 RF_HD int cl_order(int i) {
@@ -228,93 +241,105 @@ template <class Src, class Sink, class W> RF_HD int inflate_codes(BitReader<Src>
     }
 }
 
-// Blocks from the reader's position.  whole = false (a piece of the segmented plan) also stops, with *ended = 2, behind a non-final stored
-// block that is empty or that fills the sink to its cap: both end on a byte boundary with nothing pending.  *ended = 1: the final block is done.
-// Bound: every block consumes at least its 3 header bits.
+// One block from the reader's position.  *fin: its BFINAL bit.  *piece_end (whole = false, a piece of the segmented plan): the block was a
+// non-final stored block that is empty or that fills the sink to its cap; both end on a byte boundary with nothing pending.
+template <class Src, class Sink, class W> RF_HD int inflate_block(BitReader<Src>& br, Sink& sink, Tables* t, bool whole, int* fin_out, int* piece_end) {
+    *fin_out = 0;
+    *piece_end = 0;
+    if (!br.need(3)) return E_TRUNCATED;
+    const int fin = (int)br.take(1), type = (int)br.take(2);
+    W::note_block(type);
+    if (type == 0) {
+        br.align();
+        if (!br.need(32)) return E_TRUNCATED;
+        const uint32_t len = br.take(16), nlen = br.take(16);
+        if ((len ^ 0xffffu) != nlen) return E_STORED_LEN;
+        const uint32_t p = br.bytepos();
+        if (len > br.src.size() - p) return E_TRUNCATED;          // p <= size()
+        if (len > sink.cap() - sink.produced()) return E_TOO_LONG;
+        sink.copy(br.src, p, len);
+        br.seek(p + len);
+        if (len == 0) W::note_empty_stored();
+        if (!whole && !fin && (len == 0 || sink.produced() == sink.cap())) *piece_end = 1;
+    } else if (type == 1) {
+        W::sync();
+        if (W::leader()) {
+            for (int i = 0; i < 288; ++i) t->lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8);
+            for (int i = 288; i < 320; ++i) t->lens[i] = 5;
+        }
+        huff_build<W>(&t->lit, t->lens, 288, &t->rc);
+        huff_build<W>(&t->dist, t->lens + 288, 32, &t->rc);
+        const int rc = inflate_codes<Src, Sink, W>(br, sink, t);
+        if (rc) return rc;
+    } else if (type == 2) {
+        if (!br.need(14)) return E_TRUNCATED;
+        const int nlen = (int)br.take(5) + 257, ndist = (int)br.take(5) + 1, ncode = (int)br.take(4) + 4;
+        if (nlen > 286 || ndist > 30) return E_CODE_LENGTHS;
+        W::sync();
+        if (W::leader())
+            for (int i = 0; i < 19; ++i) t->lens[i] = 0;
+        for (int i = 0; i < ncode; ++i) {          // <= 19 iterations
+            if (!br.need(3)) return E_TRUNCATED;
+            const uint32_t v = br.take(3);
+            if (W::leader()) t->lens[cl_order(i)] = (uint8_t)v;
+        }
+        if (huff_build<W>(&t->dist, t->lens, 19, &t->rc) != 0) return E_CODE_LENGTHS;          // zlib: the code-length code must be complete
+        int idx = 0, last = 0;
+        while (idx < nlen + ndist) {          // every iteration consumes at least one bit or leaves
+            const int s = huff_decode(&t->dist, br);
+            if (s < 0) return -s;
+            if (s < 16) {
+                if (W::leader()) t->lens[idx] = (uint8_t)s;
+                last = s;
+                ++idx;
+                continue;
+            }
+            int rep, val = 0;
+            if (s == 16) {
+                if (idx == 0) return E_CODE_LENGTHS;
+                if (!br.need(2)) return E_TRUNCATED;
+                val = last;
+                rep = 3 + (int)br.take(2);
+            } else if (s == 17) {
+                if (!br.need(3)) return E_TRUNCATED;
+                rep = 3 + (int)br.take(3);
+            } else {
+                if (!br.need(7)) return E_TRUNCATED;
+                rep = 11 + (int)br.take(7);
+            }
+            if (idx + rep > nlen + ndist) return E_CODE_LENGTHS;
+            if (W::leader())
+                for (int k = 0; k < rep; ++k) t->lens[idx + k] = (uint8_t)val;          // idx + rep <= 316 < 320
+            idx += rep;
+            last = val;
+        }
+        W::sync();
+        if (t->lens[256] == 0) return E_CODE_LENGTHS;          // no end-of-block code
+        note_lengths<W>(t->lens, nlen + ndist);
+        int rc = huff_build<W>(&t->lit, t->lens, nlen, &t->rc);
+        if (rc < 0 || rc == 2) return E_CODE_LENGTHS;
+        rc = huff_build<W>(&t->dist, t->lens + nlen, ndist, &t->rc);
+        if (rc < 0 || rc == 2) return E_CODE_LENGTHS;
+        rc = inflate_codes<Src, Sink, W>(br, sink, t);
+        if (rc) return rc;
+    } else {
+        return E_BLOCK_TYPE;
+    }
+    *fin_out = fin;
+    return OK;
+}
+
+// Blocks from the reader's position.  whole = false also stops, with *ended = 2, behind a block that set *piece_end.  *ended = 1: the final
+// block is done.  Bound: every block consumes at least its 3 header bits.
 template <class Src, class Sink, class W> RF_HD int inflate_blocks(BitReader<Src>& br, Sink& sink, Tables* t, bool whole, int* ended) {
     *ended = 0;
     for (;;) {
-        if (!br.need(3)) return E_TRUNCATED;
-        const int fin = (int)br.take(1), type = (int)br.take(2);
-        W::note_block(type);
-        if (type == 0) {
-            br.align();
-            if (!br.need(32)) return E_TRUNCATED;
-            const uint32_t len = br.take(16), nlen = br.take(16);
-            if ((len ^ 0xffffu) != nlen) return E_STORED_LEN;
-            const uint32_t p = br.bytepos();
-            if (len > br.src.size() - p) return E_TRUNCATED;          // p <= size()
-            if (len > sink.cap() - sink.produced()) return E_TOO_LONG;
-            sink.copy(br.src, p, len);
-            br.seek(p + len);
-            if (len == 0) W::note_empty_stored();
-            if (!whole && !fin && (len == 0 || sink.produced() == sink.cap())) {
-                *ended = 2;
-                return OK;
-            }
-        } else if (type == 1) {
-            W::sync();
-            if (W::leader()) {
-                for (int i = 0; i < 288; ++i) t->lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8);
-                for (int i = 288; i < 320; ++i) t->lens[i] = 5;
-            }
-            huff_build<W>(&t->lit, t->lens, 288, &t->rc);
-            huff_build<W>(&t->dist, t->lens + 288, 32, &t->rc);
-            const int rc = inflate_codes<Src, Sink, W>(br, sink, t);
-            if (rc) return rc;
-        } else if (type == 2) {
-            if (!br.need(14)) return E_TRUNCATED;
-            const int nlen = (int)br.take(5) + 257, ndist = (int)br.take(5) + 1, ncode = (int)br.take(4) + 4;
-            if (nlen > 286 || ndist > 30) return E_CODE_LENGTHS;
-            W::sync();
-            if (W::leader())
-                for (int i = 0; i < 19; ++i) t->lens[i] = 0;
-            for (int i = 0; i < ncode; ++i) {          // <= 19 iterations
-                if (!br.need(3)) return E_TRUNCATED;
-                const uint32_t v = br.take(3);
-                if (W::leader()) t->lens[cl_order(i)] = (uint8_t)v;
-            }
-            if (huff_build<W>(&t->dist, t->lens, 19, &t->rc) != 0) return E_CODE_LENGTHS;          // zlib: the code-length code must be complete
-            int idx = 0, last = 0;
-            while (idx < nlen + ndist) {          // every iteration consumes at least one bit or leaves
-                const int s = huff_decode(&t->dist, br);
-                if (s < 0) return -s;
-                if (s < 16) {
-                    if (W::leader()) t->lens[idx] = (uint8_t)s;
-                    last = s;
-                    ++idx;
-                    continue;
-                }
-                int rep, val = 0;
-                if (s == 16) {
-                    if (idx == 0) return E_CODE_LENGTHS;
-                    if (!br.need(2)) return E_TRUNCATED;
-                    val = last;
-                    rep = 3 + (int)br.take(2);
-                } else if (s == 17) {
-                    if (!br.need(3)) return E_TRUNCATED;
-                    rep = 3 + (int)br.take(3);
-                } else {
-                    if (!br.need(7)) return E_TRUNCATED;
-                    rep = 11 + (int)br.take(7);
-                }
-                if (idx + rep > nlen + ndist) return E_CODE_LENGTHS;
-                if (W::leader())
-                    for (int k = 0; k < rep; ++k) t->lens[idx + k] = (uint8_t)val;          // idx + rep <= 316 < 320
-                idx += rep;
-                last = val;
-            }
-            W::sync();
-            if (t->lens[256] == 0) return E_CODE_LENGTHS;          // no end-of-block code
-            note_lengths<W>(t->lens, nlen + ndist);
-            int rc = huff_build<W>(&t->lit, t->lens, nlen, &t->rc);
-            if (rc < 0 || rc == 2) return E_CODE_LENGTHS;
-            rc = huff_build<W>(&t->dist, t->lens + nlen, ndist, &t->rc);
-            if (rc < 0 || rc == 2) return E_CODE_LENGTHS;
-            rc = inflate_codes<Src, Sink, W>(br, sink, t);
-            if (rc) return rc;
-        } else {
-            return E_BLOCK_TYPE;
+        int fin, piece_end;
+        const int rc = inflate_block<Src, Sink, W>(br, sink, t, whole, &fin, &piece_end);
+        if (rc) return rc;
+        if (piece_end) {
+            *ended = 2;
+            return OK;
         }
         if (fin) {
             *ended = 1;

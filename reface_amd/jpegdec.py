@@ -587,9 +587,9 @@ class FileDecoder:
     item to the decoder of its signature; a file of a kind that is not enabled, or of neither kind, is decoded by PIL.  ``kinds`` is what
     ``pngdec.ByteFolder`` asks to know which files travel as bytes."""
 
-    def __init__(self, device="cuda", png=False, jpeg=False, jpeg_parallel=False):
+    def __init__(self, device="cuda", png=False, jpeg=False, jpeg_parallel=False, png_parallel=False):
         self.device = torch.device(device)
-        self.png = pngdec.PngDecoder(device) if png else None
+        self.png = pngdec.PngDecoder(device, parallel=png_parallel) if png else None
         self.jpeg = JpegDecoder(device, parallel=jpeg_parallel) if jpeg else None
         self.kinds = tuple(k for k, d in (("png", self.png), ("jpeg", self.jpeg)) if d is not None)
 

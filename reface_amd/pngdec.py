@@ -11,6 +11,12 @@ independently decodable pieces as ``--gpu_png`` writes them: the host lists the 
 one wave decodes from each, and the device accepts the file only if the pieces chain up exactly; otherwise the serial plan decodes it, in the
 same launch sequence, without a host round trip.
 
+A third plan, ``"blocks"``, is an opt-in (``PngDecoder(parallel=True)``, the callers' ``--gpu_png_parallel``) for the streams every other
+writer leaves, which have no such markers: zlib starts a new dynamic Huffman block every few tens of KB, so the device looks for dynamic
+block headers at every bit offset, decodes from every one it finds, and accepts the file only if the chunks chain up from the stream start to
+the final block and the resolved bytes have the trailer's Adler-32 (``rf_png_inflate_blocks``; reface_amd/csrc/png_blocks.h).  The plan only
+accepts: a file it does not take is decoded by the serial plan in the same launch sequence, so arrays and error codes are the same.
+
 ``PngDecoder.decode_async`` enqueues everything on the current stream and returns at once; ``PngDecodeJob.result()`` waits for the event,
 reads the per-file error codes and raises ``PngDecodeError`` naming the file for a damaged stream.
 """
@@ -31,6 +37,8 @@ BPP = {0: 1, 4: 2, 2: 3, 6: 4}              # PNG colour type -> bytes per pixel
 MARKER = b"\x00\x00\xff\xff"
 MAX_WIDTH = 8192                            # rf_png_unfilter_u8 keeps one row of packed pixels in LDS (32 KiB)
 MAX_HEIGHT = 1 << 20                        # rf_png_unfilter_u8 refuses more rows
+PLANS = {0: "serial", 1: "segments", 2: "blocks"}          # the plan word of the status
+BLOCKS_MAX_STREAM = 1 << 28                                  # longer streams are not eligible for the blocks plan: bit offsets stay below 2^31
 ERRORS = {1: "the stream is truncated", 2: "bad zlib header", 3: "invalid block type", 4: "stored block length mismatch",
           5: "invalid code lengths", 6: "invalid code", 7: "distance beyond the start of the output", 8: "more data than the image holds",
           9: "less data than the image holds", 10: "Adler-32 mismatch", 11: "filter type above 4"}
@@ -141,6 +149,12 @@ def counts_line(decoder, what="files"):
     return f"gpu_png_decode: {decoder.counts['gpu']} {what} decoded on the device, {decoder.counts['host']} on the host"
 
 
+def _check_block_bytes(block_bytes):
+    if int(block_bytes) != block_bytes or not 16 <= block_bytes <= 1 << 20:
+        raise ValueError(f"PngDecoder: block_bytes must be an integer in 16 .. 2^20, got {block_bytes!r}")
+    return int(block_bytes)
+
+
 def _up16(n):
     return (n + 15) // 16 * 16
 
@@ -188,9 +202,10 @@ class PngDecodeJob:
     """One enqueued decode; ``result()`` (any thread, once) gives the uint8 device tensors [H, W, C] in the order of the items, ``report``
     (complete after ``result()``) says per file where it was decoded and by which inflate plan."""
 
-    def __init__(self, dec, names, outs, gpu_idx, status, event, staging, keep, report):
+    def __init__(self, dec, names, outs, gpu_idx, status, event, staging, keep, report, blocks=None):
         self.dec, self.names, self.outs, self.gpu_idx, self.status, self.event = dec, names, outs, gpu_idx, status, event
         self.staging, self.keep, self.report = staging, keep, report
+        self.blocks = blocks       # (the work buffer, the files' capacities) of a launch with the blocks plan on, else None
         self.batch = None          # the [B, H, W, C] tensor the images are views of, when all of them came from the device at one shape
 
     def discard(self):
@@ -208,9 +223,12 @@ class PngDecodeJob:
             if self.event is not None:
                 self.event.synchronize()
                 st = self.status.cpu().tolist()
+                fields = _block_fields(self.blocks, st)
                 for k, i in enumerate(self.gpu_idx):
-                    self.report[i]["plan"] = "segments" if st[2 * k + 1] == 1 else "serial"
+                    self.report[i]["plan"] = PLANS[st[2 * k + 1]]
                     self.report[i]["code"] = st[2 * k]
+                    if fields is not None:
+                        self.report[i].update(fields[k])
                 for k, i in enumerate(self.gpu_idx):
                     if st[2 * k] != 0:
                         raise PngDecodeError(self.names[i], st[2 * k])
@@ -219,14 +237,30 @@ class PngDecodeJob:
             self._release()
 
 
+def _block_fields(blocks, st):
+    """The report fields of the blocks plan, per file of a launch: the chain's length, the candidates found (candidate 0 among them) and
+    whether an eligible file ended on the serial plan.  None when the plan was off."""
+    if blocks is None:
+        return None
+    work, caps = blocks
+    wk = work[:4 * len(caps)].cpu().tolist()
+    return [{"chunks": wk[4 * k + 1] if st[2 * k + 1] == 2 else 0, "candidates": 1 + wk[4 * k] if c else 0, "fallback": bool(c) and st[2 * k + 1] == 0}
+            for k, c in enumerate(caps)]
+
+
 class PngDecoder:
     """``decode(items, mode=None) -> list of uint8 device tensors [H, W, C]``: items are paths or ``bytes``; ``mode`` in (None, "RGB", "L")
-    reproduces ``Image.open(p)`` and ``.convert(mode)``."""
+    reproduces ``Image.open(p)`` and ``.convert(mode)``.  ``parallel`` turns the blocks plan on for streams of at least ``min_bytes`` of
+    output; a file has ``16 + len(stream) // block_bytes`` candidate slots and is left to the serial plan when the device finds more."""
 
     MAX_FREE = 4
 
-    def __init__(self, device="cuda"):
+    def __init__(self, device="cuda", parallel=False, block_bytes=1024, min_bytes=65536):
         self.device = torch.device(device)
+        self.parallel = bool(parallel)
+        self.block_bytes, self.min_bytes = _check_block_bytes(block_bytes), int(min_bytes)
+        if self.min_bytes < 1:
+            raise ValueError(f"PngDecoder: min_bytes must be at least 1, got {min_bytes}")
         self._free, self._lock = [], threading.Lock()
         self.counts = {"gpu": 0, "host": 0}          # files decoded so far, by where (the callers print them)
 
@@ -243,10 +277,11 @@ class PngDecoder:
             if len(self._free) < self.MAX_FREE:
                 self._free.append(s)
 
-    def _launch(self, streams, dims, out_cs, misalign=0, out=None, candidates=True, lengths=None):
+    def _launch(self, streams, dims, out_cs, misalign=0, out=None, candidates=True, lengths=None, parallel=None, block_bytes=None):
         """Enqueue inflate + unfilter of zlib streams: dims[i] = (H, W, bpp).  -> _Launched.
         `out` (tests): a uint8 device tensor [B, H', W', C] with H' >= H, W' >= W whose [:, :H, :W] view receives the images.
-        `lengths` (tests): the expected lengths of plain byte streams; then only the inflate stage runs and dims / out_cs are not used."""
+        `lengths` (tests): the expected lengths of plain byte streams; then only the inflate stage runs and dims / out_cs are not used.
+        `parallel`, `block_bytes`: overrides of the decoder's own."""
         lib = _lib.load()
         B = len(streams)
         pixels = lengths is None
@@ -260,8 +295,13 @@ class PngDecoder:
             # a false candidate costs a wave: a stream with far more markers than segments is left to the serial plan
             cands.append([2] + c if c and len(c) <= 4 * (n // SEG + 2) else [])
         ncand = sum(len(c) for c in cands)
-        desc_bytes, cand_bytes = B * DESC * 8, _up16(2 * ncand * 4)
-        comp_off, o = [], desc_bytes + cand_bytes
+        parallel = self.parallel if parallel is None else bool(parallel)
+        bb = self.block_bytes if block_bytes is None else _check_block_bytes(block_bytes)
+        # the blocks plan: the capacity in candidate slots of every eligible file (0: not eligible)
+        caps = [16 + len(z) // bb if parallel and n >= self.min_bytes and len(z) < BLOCKS_MAX_STREAM else 0 for z, n in zip(streams, lengths)]
+        nslot = sum(caps)
+        desc_bytes, cand_bytes, blk_bytes = B * DESC * 8, _up16(2 * ncand * 4), _up16((3 * B + nslot) * 4) if parallel else 0
+        comp_off, o = [], desc_bytes + cand_bytes + blk_bytes
         for z in streams:
             comp_off.append(o + misalign)
             o = _up16(o + misalign + len(z))
@@ -290,12 +330,21 @@ class PngDecoder:
         cand = sg.a[desc_bytes:desc_bytes + 2 * ncand * 4].view(np.int32).reshape(2, ncand)
         cb = 0
         for b, (z, (H, W, bpp)) in enumerate(zip(streams, dims)):
-            desc[b] = (comp_off[b] - desc_bytes - cand_bytes, len(z), filt_off[b], lengths[b], H, W, bpp, out_cs[b], pix_off[b], rstride[b], cb,
+            desc[b] = (comp_off[b] - desc_bytes - cand_bytes - blk_bytes, len(z), filt_off[b], lengths[b], H, W, bpp, out_cs[b], pix_off[b], rstride[b], cb,
                        len(cands[b]))
             cand[0, cb:cb + len(cands[b])] = b
             cand[1, cb:cb + len(cands[b])] = cands[b]
             cb += len(cands[b])
             sg.a[comp_off[b]:comp_off[b] + len(z)] = np.frombuffer(z, dtype=np.uint8)
+        bm_words = 0
+        if parallel:
+            blk = sg.a[desc_bytes + cand_bytes:desc_bytes + cand_bytes + (3 * B + nslot) * 4].view(np.int32)
+            sb = 0
+            for b, (z, c) in enumerate(zip(streams, caps)):
+                blk[3 * b:3 * b + 3] = (c, sb, bm_words) if c else (0, 0, 0)
+                blk[3 * B + sb:3 * B + sb + c] = b
+                sb += c
+                bm_words += (len(z) + 3) // 4 if c else 0
         dev = self.device
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev)
@@ -307,10 +356,19 @@ class PngDecoder:
             status = torch.empty(2 * B, dtype=torch.int32, device=dev)
             pix = out if out is not None else torch.empty(max(pix_bytes, 1), dtype=torch.uint8, device=dev)
             base = up.data_ptr()
-            comp_ptr, comp_bytes = base + desc_bytes + cand_bytes, total - desc_bytes - cand_bytes
-            _lib.check(lib.rf_png_inflate(comp_ptr, comp_bytes, desc.ctypes.data, base, B, filt.data_ptr(), filt.numel(),
-                                          cand.ctypes.data if ncand else None, base + desc_bytes if ncand else None, ncand,
-                                          slots.data_ptr(), pieces.data_ptr(), status.data_ptr(), st.cuda_stream), "rf_png_inflate")
+            comp_ptr, comp_bytes = base + desc_bytes + cand_bytes + blk_bytes, total - desc_bytes - cand_bytes - blk_bytes
+            args = (comp_ptr, comp_bytes, desc.ctypes.data, base, B, filt.data_ptr(), filt.numel(), cand.ctypes.data if ncand else None,
+                    base + desc_bytes if ncand else None, ncand, slots.data_ptr(), pieces.data_ptr(), status.data_ptr())
+            work = None
+            if parallel:
+                bitmap = torch.empty(max(bm_words, 1), dtype=torch.int32, device=dev)
+                work = torch.empty(4 * B + 11 * nslot, dtype=torch.int32, device=dev)
+                marks = torch.empty(filt.numel() if nslot else 1, dtype=torch.int16, device=dev)          # 2 bytes per output byte
+                _lib.check(lib.rf_png_inflate_blocks(*args, blk.ctypes.data, base + desc_bytes + cand_bytes, nslot, bitmap.data_ptr(), bitmap.numel(),
+                                                     work.data_ptr(), work.numel(), marks.data_ptr(), marks.numel(), st.cuda_stream), "rf_png_inflate_blocks")
+            else:
+                bitmap = marks = None
+                _lib.check(lib.rf_png_inflate(*args, st.cuda_stream), "rf_png_inflate")
             if pixels:
                 _lib.check(lib.rf_png_unfilter_u8(filt.data_ptr(), filt.numel(), desc.ctypes.data, base, B, pix.data_ptr(), pix_bytes, status.data_ptr(),
                                                   st.cuda_stream), "rf_png_unfilter_u8")
@@ -322,8 +380,8 @@ class PngDecoder:
         elif pixels:
             images = [pix[pix_off[b]:pix_off[b] + d[0] * d[1] * c].view(d[0], d[1], c) for b, (d, c) in enumerate(zip(dims, out_cs))]
             batch = pix.view(B, dims[0][0], dims[0][1], out_cs[0]) if same else None
-        return _Launched(images=images, status=status, event=ev, staging=sg, keep=(up, filt, slots, pieces, pix), batch=batch, filt=filt,
-                         filt_off=filt_off)
+        return _Launched(images=images, status=status, event=ev, staging=sg, keep=(up, filt, slots, pieces, pix, bitmap, work, marks), batch=batch, filt=filt,
+                         filt_off=filt_off, blocks=(work, caps) if parallel else None)
 
     def decode_async(self, items, mode=None):
         names, datas = [], []
@@ -363,7 +421,7 @@ class PngDecoder:
         L = self._launch(streams, dims, out_cs)
         for k, i in enumerate(gpu_idx):
             outs[i] = L.images[k]
-        job = PngDecodeJob(self, names, outs, gpu_idx, L.status, L.event, L.staging, L.keep, report)
+        job = PngDecodeJob(self, names, outs, gpu_idx, L.status, L.event, L.staging, L.keep, report, L.blocks)
         job.batch = L.batch if len(gpu_idx) == len(datas) else None
         return job
 
@@ -371,18 +429,21 @@ class PngDecoder:
         return self.decode_async(items, mode).result()
 
     # ---- the two stages alone (tests, tools/pngdec_rate.py)
-    def inflate(self, streams, lengths, misalign=0, check=True):
+    def inflate(self, streams, lengths, misalign=0, check=True, parallel=None, block_bytes=None):
         """zlib streams of the given output lengths -> (list of uint8 device tensors, report).  `misalign` shifts every stream off its
         16-byte aligned place in the upload.  A damaged stream raises PngDecodeError naming its index, or, with check=False, only leaves
-        its error code in the report."""
-        L = self._launch([bytes(z) for z in streams], None, None, misalign=misalign, lengths=list(lengths))
+        its error code in the report.  `parallel` and `block_bytes` override the decoder's own (tests, tools/pngdec_rate.py)."""
+        L = self._launch([bytes(z) for z in streams], None, None, misalign=misalign, lengths=list(lengths), parallel=parallel, block_bytes=block_bytes)
         filt, filt_off = L.filt, L.filt_off
         try:
             L.event.synchronize()
             st = L.status.cpu().tolist()
+            fields = _block_fields(L.blocks, st)
         finally:
             self._release(L.staging)
-        report = [{"where": "gpu", "plan": "segments" if st[2 * k + 1] == 1 else "serial", "code": st[2 * k]} for k in range(len(streams))]
+        report = [{"where": "gpu", "plan": PLANS[st[2 * k + 1]], "code": st[2 * k]} for k in range(len(streams))]
+        for k, r in enumerate(report if fields is not None else ()):
+            r.update(fields[k])
         for k in range(len(streams)):
             if check and st[2 * k] != 0:
                 raise PngDecodeError(f"<stream #{k}>", st[2 * k])

@@ -140,6 +140,9 @@ def build_parser():
                    "<video>_inv_transforms.npy and temp_results/)")
     p.add_argument("--gpu_png_decode", action="store_true", help="--paste_back / --stream: decode the video's frames on the GPU "
                    "(reface_amd/pngdec.py) and hand them to the device chain as device tensors; the files written are the same")
+    p.add_argument("--gpu_png_parallel", action="store_true", help="--gpu_png_decode: frames that --gpu_png did not write (extracted video frames) "
+                   "are inflated by one wave per dynamic Huffman block (the blocks plan of reface_amd/pngdec.py) instead of one wave per frame; "
+                   "the frames are the same")
     p.add_argument("--gpu_png", action="store_true", help="--paste_back / --stream: encode the pasted RGBA frames of results/ on the GPU "
                    "(reface_amd/pngenc.py): the same pixels, other file bytes (about zlib level 1 in size); crops, label maps and model_outputs "
                    "stay on the host writer")
@@ -169,7 +172,7 @@ def build_parser():
     return p
 
 
-VIDEO_OPTIONS = ("write_video", "video_fps", "video_quality", "video_subsampling", "video_in", "gpu_jpeg_parallel")
+VIDEO_OPTIONS = ("write_video", "video_fps", "video_quality", "video_subsampling", "video_in", "gpu_jpeg_parallel", "gpu_png_parallel")
 _READERS = {}
 
 
@@ -422,7 +425,7 @@ def make_png_decoder(opt, device):
     if not opt.gpu_png_decode:
         return None
     from reface_amd.pngdec import PngDecoder
-    return PngDecoder(device)
+    return PngDecoder(device, parallel=opt.gpu_png_parallel)
 
 
 def decoder_line(opt, decoder):
@@ -474,6 +477,9 @@ def main(argv=None):
     if opt.gpu_png_decode and not (opt.paste_back or opt.stream or opt.stream_keep):
         raise SystemExit("inference_swap_video: --gpu_png_decode decodes the video's frames for --paste_back or --stream; without either no frame "
                          "is read (the crops of target_frames/ go through the dataset's host transforms)")
+    if opt.gpu_png_parallel and not opt.gpu_png_decode:
+        raise SystemExit("inference_swap_video: --gpu_png_parallel chooses a plan of the GPU PNG decoder and needs --gpu_png_decode; without it no PNG "
+                         "frame is decoded on the GPU")
     if opt.gpu_png and opt.skip_save:
         print("inference_swap_video: --skip_save writes no files, so --gpu_png has nothing to encode")
     if opt.paste_mask and not (opt.paste_back or opt.stream or opt.stream_keep):

@@ -10,7 +10,12 @@ Per workload, one JSON line each: the decoder's wall time per batch as a caller 
 the HIP-event time of the same loop, the inflate plan taken; in a child of its own under rocprofv3 --kernel-trace --stats the time per
 kernel; and the wall time of PIL decoding the same bytes in a pool of 16 processes.  Every run is a child process under its own time limit.
 
-Usage: python tools/pngdec_rate.py [--iters 20] [--out out/pngdec_rate] [--no-rocprof]
+With --parallel every workload is decoded with the blocks plan off (``PngDecoder(parallel=False)``: the serial plan for PIL's files) and on
+(``parallel=True``), the settings alternating in --rounds rounds inside one child; the lines give the median [min .. max] of the rounds per
+setting, the plans taken, the chain chunks per file, the false candidates per MB of compressed data and the fallbacks.  frames1080 is also
+run at block_bytes 256 and 4096.  PIL decodes the same bytes in 1 and in 16 processes, and the kernel trace is taken with the plan on.
+
+Usage: python tools/pngdec_rate.py [--parallel] [--rounds 5] [--iters 20] [--out out/pngdec_rate] [--no-rocprof]
 """
 import argparse
 import csv
@@ -60,30 +65,49 @@ def files(name):
     return [distinct[k % len(distinct)] for k in range(n)], imgs
 
 
+def settings_of(a):
+    """(name, PngDecoder keywords) of the settings one GPU child alternates between"""
+    out = [("serial", dict(parallel=False))]
+    if a.parallel:
+        out.append(("blocks", dict(parallel=True)))
+        if a.workload == "frames1080":
+            out += [(f"blocks{bb}", dict(parallel=True, block_bytes=bb)) for bb in (256, 4096)]
+    return [s for s in out if a.only is None or s[0] == a.only]
+
+
 def child_gpu(a):
     import torch
     from reface_amd.pngdec import PngDecoder
     batch, imgs = files(a.workload)
-    dec = PngDecoder("cuda")
-    job = dec.decode_async(batch)
-    outs = job.result()
-    for k, o in enumerate(outs):
-        assert np.array_equal(o.cpu().numpy(), imgs[k % len(imgs)]), k
-    plans = sorted({r["plan"] for r in job.report})
-    where = sorted({r["where"] for r in job.report})
-    torch.cuda.synchronize()
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    w0 = time.perf_counter()
-    t0.record()
-    for _ in range(a.iters):
-        dec.decode(batch)
-    t1.record()
-    t1.synchronize()
-    wall = (time.perf_counter() - w0) / a.iters * 1e3
+    png_bytes = sum(len(f) for f in batch)
     raw = sum(int(np.prod(imgs[k % len(imgs)].shape)) for k in range(len(batch)))
-    print(json.dumps({"metric": "gpu_png_decode", "workload": a.workload, "files": len(batch), "png_bytes": sum(len(f) for f in batch), "raw_bytes": raw,
-                      "where": where, "plan": plans, "iters": a.iters, "wall_ms_per_batch": round(wall, 3),
-                      "event_ms_per_batch": round(t0.elapsed_time(t1) / a.iters, 3), "files_per_s": round(len(batch) / wall * 1e3, 1)}))
+    decs, info, times = {}, {}, {}
+    for name, kw in settings_of(a):          # every setting decodes the batch once and must give the images
+        dec = decs[name] = PngDecoder("cuda", **kw)
+        job = dec.decode_async(batch)
+        outs = job.result()
+        for k, o in enumerate(outs):
+            assert np.array_equal(o.cpu().numpy(), imgs[k % len(imgs)]), (name, k)
+        rep = job.report
+        info[name] = {"where": sorted({r["where"] for r in rep}), "plan": sorted({r["plan"] for r in rep})}
+        if dec.parallel:
+            false = sum(r["candidates"] - r["chunks"] for r in rep if r["plan"] == "blocks")
+            info[name].update(block_bytes=dec.block_bytes, chunks_per_file=round(sum(r["chunks"] for r in rep) / len(rep), 1),
+                              false_candidates_per_mb=round(false / (png_bytes / 1e6), 3), fallbacks=sum(bool(r["fallback"]) for r in rep))
+        times[name] = []
+    for _ in range(a.rounds):          # the settings alternate: a drift of the box shows in every one of them
+        for name, dec in decs.items():
+            torch.cuda.synchronize()
+            w0 = time.perf_counter()
+            for _ in range(a.iters):
+                dec.decode(batch)
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - w0) / a.iters * 1e3)
+    for name, t in times.items():
+        med = float(np.median(t))
+        print(json.dumps({"metric": "gpu_png_decode", "workload": a.workload, "setting": name, "files": len(batch), "png_bytes": png_bytes, "raw_bytes": raw,
+                          **info[name], "rounds": a.rounds, "iters": a.iters, "wall_ms_per_batch": round(med, 3),
+                          "wall_ms_range": [round(min(t), 3), round(max(t), 3)], "files_per_s": round(len(batch) / med * 1e3, 1)}))
     with open(a.files_out, "wb") as f:          # the same bytes go to the host child
         import pickle
         pickle.dump(batch, f)
@@ -98,17 +122,17 @@ def child_host(a):
     import multiprocessing as mp
     import pickle
     batch = pickle.load(open(a.files_out, "rb"))
-    with mp.Pool(HOST_PROCS) as pool:
-        pool.map(_pil_one, batch[:HOST_PROCS])          # the workers exist and have PIL loaded before the clock starts
+    with mp.Pool(a.procs) as pool:
+        pool.map(_pil_one, batch[:a.procs])          # the workers exist and have PIL loaded before the clock starts
         t0 = time.perf_counter()
         for _ in range(a.iters):
-            pool.map(_pil_one, batch, chunksize=max(1, len(batch) // (4 * HOST_PROCS)))
+            pool.map(_pil_one, batch, chunksize=max(1, len(batch) // (4 * a.procs)))
         wall = (time.perf_counter() - t0) / a.iters * 1e3
     t1 = time.thread_time()
     for d in batch[:8]:
         _pil_one(d)
     per = (time.thread_time() - t1) / min(8, len(batch)) * 1e3
-    print(json.dumps({"metric": "pil_png_decode", "workload": a.workload, "files": len(batch), "processes": HOST_PROCS, "iters": a.iters,
+    print(json.dumps({"metric": "pil_png_decode", "workload": a.workload, "files": len(batch), "processes": a.procs, "iters": a.iters,
                       "wall_ms_per_batch": round(wall, 3), "files_per_s": round(len(batch) / wall * 1e3, 1), "thread_ms_per_file": round(per, 3)}))
 
 
@@ -130,7 +154,13 @@ def main():
     ap.add_argument("--child", type=str, default=None, choices=["gpu", "host"])
     ap.add_argument("--workload", type=str, default="pil512", choices=WORKLOADS)
     ap.add_argument("--files-out", dest="files_out", type=str, default=None)
+    ap.add_argument("--parallel", action="store_true", help="also decode with the blocks plan (PngDecoder(parallel=True)), alternating with the serial plan")
+    ap.add_argument("--rounds", type=int, default=None, help="rounds the settings alternate in (default: 5 with --parallel, else 1)")
+    ap.add_argument("--only", type=str, default=None, help="(child) one setting alone: serial, blocks, blocks256, blocks4096")
+    ap.add_argument("--procs", type=int, default=HOST_PROCS, help="(child) PIL's worker processes")
     a = ap.parse_args()
+    if a.rounds is None:
+        a.rounds = 5 if a.parallel else 1
     if a.child == "gpu":
         return child_gpu(a)
     if a.child == "host":
@@ -147,18 +177,20 @@ def main():
 
     for wl in WORKLOADS:
         fo = os.path.join(a.out, wl + ".files.pkl")
-        keep(run_child(me + ["--child", "gpu", "--workload", wl, "--iters", str(a.iters), "--files-out", fo], 300))
-        keep(run_child(me + ["--child", "host", "--workload", wl, "--iters", str(max(2, a.iters // 4)), "--files-out", fo], 300))
+        par = ["--parallel"] if a.parallel else []
+        keep(run_child(me + ["--child", "gpu", "--workload", wl, "--iters", str(a.iters), "--rounds", str(a.rounds), "--files-out", fo] + par, 900))
+        for procs in ((1, HOST_PROCS) if a.parallel else (HOST_PROCS,)):
+            keep(run_child(me + ["--child", "host", "--workload", wl, "--iters", str(max(2, a.iters // 4)), "--procs", str(procs), "--files-out", fo], 300))
         if not a.no_rocprof:          # a run of its own: the kernel trace slows the host side, so its numbers are not mixed with the timing above
             d = os.path.join(a.out, "trace_" + wl)
             run_child(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"] + me +
-                      ["--child", "gpu", "--workload", wl, "--iters", "5", "--files-out", fo], 600)
+                      ["--child", "gpu", "--workload", wl, "--iters", "5", "--rounds", "1", "--files-out", fo] + (par + ["--only", "blocks"] if par else []), 600)
             stats = sorted(glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True))
             per = {}
             for row in csv.DictReader(open(stats[0])) if stats else []:
                 if "png_" in row.get("Name", ""):
                     per[row["Name"].split("(")[0]] = {"calls": int(row["Calls"]), "avg_us": round(float(row["AverageNs"]) / 1e3, 2)}
-            keep(json.dumps({"metric": "gpu_png_decode_kernels", "workload": wl, "kernels": per}))
+            keep(json.dumps({"metric": "gpu_png_decode_kernels", "workload": wl, "setting": "blocks" if par else "serial", "kernels": per}))
         os.remove(fo)
     with open(os.path.join(a.out, "pngdec_rate.jsonl"), "w") as f:
         f.write("\n".join(lines) + "\n")
