@@ -49,6 +49,10 @@ int rf_version(void);
  * optionally nearest-upsampled x2 on the fly (`ups`) and optionally the channel concatenation of two
  * sources [src0 | src1] (UNet skip connections).  KH = KW = 1 with B*Hin*Win = M gives a plain GEMM
  * (nn.Linear / 1x1 conv); `batch` > 1 runs independent problems (strides in elements).
+ * Any KH x KW window (KH != KW included), any stride and any pad_t / pad_l, input pixels outside the image read as zero: the direct-to-LDS
+ * main loop takes windows with Hout <= 1024, Wout <= 1024 and fewer than 4095 samples (its packed row descriptor sample:12 | oy:10 | ox:10),
+ * the register loop everything beyond them and every K that is not whole K tiles per tap -- both pinned bit-exactly on either side of each
+ * limit and at the towers' windows (7x7 s2, 11x11 s4, 5x5, 3x3 s2, 1x1 s2, patch = stride, 3 channels stored in 4 / 8) by tests/gemm_exact_refs.py.
  *
  * Replaces: F.conv2d 3x3 / 1x1 in ResBlock, Downsample, Upsample, UNet in/out convs
  * (openaimodel.py:107,116,151-153,204,230,241,669,835), nn.Linear in attention / GEGLU / time-embed

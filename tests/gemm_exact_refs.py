@@ -8,6 +8,7 @@ MFMA shape -- is a multiple of one unit below 2^24 units: fp32 accumulation is e
                  representable in bf16 (asserted before any launch); between the two seeds every k carries a non-zero product in some row
   fp8          : e4m3 integers with per-row / per-block power-of-two scales; C = 320 cases carry the per-tap zero padding to 384
   split-bf16   : values with more than 8 significant bits (lo != 0); expected = hi hi + hi lo + lo hi in fp64 (lo lo is not formed)
+  windows      : the win-* cases walk KH x KW / stride / pad_t, pad_l at the geometries of the metric towers (TOWER_WINDOWS), dense with fp32 output
 The reference restates include/reface_hip.h's formula: explicit zero padding and slicing, nearest upsampling, channel concatenation, the tail
 source, the K orders of `korder`, then ONE fp64 matmul and the epilogue.  `mut` selects a deliberately wrong variant (MUTANTS): the CPU file
 proves that every one of them changes an output of some case."""
@@ -28,7 +29,7 @@ LN_EPS, LN_IN_COLS = 1e-5, 64          # LayerNorm consumer cases: eps, columns 
 GUARD = 64                # guard rows / elements around every output region
 INEXACT_ACTS = (ops.ACT_SILU, ops.ACT_QUICK_GELU, ops.ACT_GELU, ops.ACT_SIGMOID)
 
-_DEFAULTS = dict(op="bf16", out="f32", B=1, H=1, W=1, C0=64, C1=0, N=64, ks=1, stride=1, pad=(0, 0, 0, 0), ups=0, korder=0, Cx=0, bias=True,
+_DEFAULTS = dict(op="bf16", out="f32", B=1, H=1, W=1, C0=64, C1=0, N=64, ks=1, kh=None, kw=None, creal=0, stride=1, pad=(0, 0, 0, 0), ups=0, korder=0, Cx=0, bias=True,
                  rowvec=False, res=False, act=ops.ACT_NONE, alpha=1.0, ws=0, gn=False, ln=None, wps=False, batch=1, col0=16, ldo_extra=16,
                  sparse="W", gate_const=False, expect={}, small=None)
 
@@ -38,6 +39,12 @@ def case(id, cells, expect, **kw):
     unknown = set(kw) - set(c)
     assert not unknown, unknown
     c.update(kw)
+    # ks is the square shorthand; kh / kw name a window on their own (ks is then the side of a square one, 0 otherwise)
+    if c["kh"] is None and c["kw"] is None:
+        c["kh"] = c["kw"] = c["ks"]
+    else:
+        assert c["kh"] and c["kw"] and "ks" not in kw, id
+        c["ks"] = c["kh"] if c["kh"] == c["kw"] else 0
     c.update(id=id, cells=tuple(cells), expect=dict(expect))
     return c
 
@@ -48,13 +55,13 @@ def bk_of(c):
 
 def geom(c):
     """sizes of the GEMM view of a case"""
-    ks, s = c["ks"], c["stride"]
+    kh, kw, s = c["kh"], c["kw"], c["stride"]
     pt, pl, pb, pr = c["pad"]
     up = 2 if c["ups"] else 1
     Hs, Ws = c["H"] * up, c["W"] * up
-    Ho, Wo = (Hs + pt + pb - ks) // s + 1, (Ws + pl + pr - ks) // s + 1
+    Ho, Wo = (Hs + pt + pb - kh) // s + 1, (Ws + pl + pr - kw) // s + 1
     ctot = c["C0"] + c["C1"]
-    taps = 9 if c["ups"] == 2 else ks * ks
+    taps = 9 if c["ups"] == 2 else kh * kw
     kwin = taps * ctot
     nout = c["N"] // 2 if c["act"] == ops.ACT_GEGLU else c["N"]
     return dict(Ho=Ho, Wo=Wo, M=c["B"] * Ho * Wo, rps=Ho * Wo, ctot=ctot, taps=taps, kwin=kwin, K=kwin + c["Cx"], nout=nout)
@@ -146,6 +153,13 @@ def make_inputs(c, seed=0):
         w = _x3_values(g, (S, N, G["K"]), 1) if c["op"] == "x3" else _ints(g, (S, N, G["K"]), -3, 3)
         if sparse == "W":
             w = _keep(g, w, nnz - 1, cover=True)
+        if c["creal"]:
+            # `creal` real channels stored in C0: the activation's pad channels stay NON-zero, the weight's pad columns are zero, as
+            # ops.pack_conv_weight(cin_pad=) writes them -- a read that slips by a channel or a tap meets a live value
+            assert C1 == 0 and Cx == 0 and c["korder"] == 0
+            w = w.reshape(S, N, G["taps"], C0).clone()
+            w[..., c["creal"]:] = 0
+            w = w.reshape(S, N, G["K"])
         i["w"] = w
     if sparse == "A":
         # at most nnz non-zero A entries per GEMM row: per source pixel nnz / taps channels (window sources) resp. the rest (tail)
@@ -204,16 +218,37 @@ def split_hi_lo(x):
 MUTANTS = ("drop_last_k", "double_k_tile", "tap_transposed", "halo_from_adjacent_row", "pad_top_bottom_swapped", "phase_swapped", "phase00_padding",
            "concat_swapped", "tail_at_input_pixel", "korder_confused", "rowvec_neighbour", "residual_row_plus_1", "nsplit_bias_offset", "geglu_swapped",
            "wps_sample0", "stat_slot_plus_1", "stat_unrounded", "tile_permuted")
+# slips of the window addressing (KH x KW taps, stride, pad_t / pad_l, the channel pitch of a tap, the K tail, a split-K slice's first tap)
+WINDOW_MUTANTS = ("kh_kw_swapped", "pad_t_l_swapped", "stride_rows_only", "border_clamped", "cin_pad_ignored", "partial_tile_overread", "slice_start_tap")
+MUTANTS = MUTANTS + WINDOW_MUTANTS
 
 
-def im2col(c, x0, x1, xt, mut=None):
+def slice_starts(c, sk):
+    """first K tile of every split-K slice (gemm.hip: per = ceil(tiles / splitk), slice z starts at z per), and the tile count"""
+    nk = -(-geom(c)["K"] // bk_of(c))
+    per = -(-nk // sk)
+    return [z * per for z in range(sk) if z * per < nk], nk
+
+
+def tap_of_tile(c, ia):
+    """the window tap K tile `ia` lies in (a window whose taps hold whole K tiles): tap-major K (korder 0) or chunk-major K (korder 1)"""
+    ntap, tpt = c["kh"] * c["kw"], (c["C0"] + c["C1"]) // bk_of(c)
+    return ia % ntap if c["korder"] else ia // tpt
+
+
+def im2col(c, x0, x1, xt, mut=None, sk=1):
     """A [B Ho Wo, K] fp64 in the K order of c['korder']: k = tap * Ctot + ch (0), (chunk, tap, ch % BK) (1), (ky, chunk, kx, ch % BK) (2), then the
-    tail source's channels at the output pixel.  ups: the window runs over the nearest-2x upsampled source."""
+    tail source's channels at the output pixel.  ups: the window runs over the nearest-2x upsampled source.  The window is KH x KW, tap = ky KW + kx
+    reads input pixel (oy stride - pad_t + ky, ox stride - pad_l + kx), zero outside the image (the bottom / right padding is whatever the output
+    extent reaches: rf_conv_gemm is told pad_t and pad_l alone)."""
     G = geom(c)
-    ks, s = (3, 1) if c["ups"] == 2 else (c["ks"], c["stride"])
+    kh, kw, s = (3, 3, 1) if c["ups"] == 2 else (c["kh"], c["kw"], c["stride"])
     pt, pl, pb, pr = (1, 1, 1, 1) if c["ups"] == 2 else c["pad"]
     if mut == "pad_top_bottom_swapped":
         pt, pb = pb, pt
+    if mut == "pad_t_l_swapped":
+        pt, pl = pl, pt
+    sx = 1 if mut == "stride_rows_only" else s
     src = x0 if x1 is None else (torch.cat([x1, x0], -1) if mut == "concat_swapped" else torch.cat([x0, x1], -1))
     if c["ups"]:
         src = src.repeat_interleave(2, 1).repeat_interleave(2, 2)
@@ -224,24 +259,65 @@ def im2col(c, x0, x1, xt, mut=None):
         flat = F.pad(src.reshape(B, Hs * Ws, ct), (0, 0, pl, pr))
         rows = [flat[:, y * Ws:y * Ws + Ws + pl + pr] for y in range(Hs)]
         p = F.pad(torch.stack(rows, 1), (0, 0, 0, 0, pt, pb))
+    elif mut == "border_clamped":
+        # every tap outside the image reads the nearest pixel: replicate padding over all that the true window reaches
+        bot, rgt = max(pb, (Ho - 1) * s + kh - pt - Hs), max(pr, (Wo - 1) * s + kw - pl - Ws)
+        p = F.pad(src.permute(0, 3, 1, 2), (pl, max(0, rgt), pt, max(0, bot)), mode="replicate").permute(0, 2, 3, 1)
     else:
         p = F.pad(src, (0, 0, pl, pr, pt, pb))
-    need_h, need_w = (Ho - 1) * s + ks, (Wo - 1) * s + ks
-    p = F.pad(p, (0, 0, 0, max(0, need_w - p.shape[2]), 0, max(0, need_h - p.shape[1])))
-    taps = []
-    for ky in range(ks):
-        for kx in range(ks):
-            y, x = (kx, ky) if mut == "tap_transposed" else (ky, kx)
-            taps.append(p[:, y:y + (Ho - 1) * s + 1:s, x:x + (Wo - 1) * s + 1:s])
-    T = torch.stack(taps, 3)                                   # [B, Ho, Wo, taps, Ctot]
+
+    def tap(ky, kx):
+        """window element (ky, kx) of every output pixel [B, Ho, Wo, Ctot]; zero beyond what is padded (also for a walk that leaves the window)"""
+        need_h, need_w = ky + (Ho - 1) * s + 1, kx + (Wo - 1) * sx + 1
+        q = F.pad(p, (0, 0, 0, max(0, need_w - p.shape[2]), 0, max(0, need_h - p.shape[1])))
+        return q[:, ky:need_h:s, kx:need_w:sx]
+
+    def coords(t):
+        if mut == "kh_kw_swapped":
+            return t // kh, t % kh
+        return (t % kw, t // kw) if mut == "tap_transposed" else (t // kw, t % kw)
+    ntap, M = kh * kw, B * Ho * Wo
     ko = c["korder"] if c["ups"] != 2 else 0
     if mut == "korder_confused" and ko:
         ko = 3 - ko
-    if ko:
-        bk = bk_of(c)
-        T = T.reshape(B, Ho, Wo, ks, ks, ct // bk, bk)
-        T = T.permute(0, 1, 2, 5, 3, 4, 6) if ko == 1 else T.permute(0, 1, 2, 3, 5, 4, 6)
-    A = T.reshape(B * Ho * Wo, ks * ks * ct)
+    bk = bk_of(c)
+    if mut == "cin_pad_ignored" and c["creal"]:
+        # k decoded as (tap, channel) with the REAL channel count as a tap's pitch
+        cr = c["creal"]
+        A = torch.stack([tap(*coords(t))[..., :cr] for t in range(-(-ntap * ct // cr))], 3).reshape(M, -1)[:, :ntap * ct]
+    elif mut == "slice_start_tap" and sk > 1 and ko < 2 and ct % bk == 0:
+        # every split-K slice but the first decodes its first tap as (tap / KH, tap % KH) and walks on from there as the kernel does
+        starts, nk = slice_starts(c, sk)
+        tpt, cols = ct // bk, []
+        for z, t0 in enumerate(starts):
+            t = tap_of_tile(c, t0)
+            ic = t0 // ntap if ko else t0 - t * tpt
+            ty, tx = (t // kh, t % kh) if z else (t // kw, t % kw)
+            for _ in range(min(nk, starts[z + 1] if z + 1 < len(starts) else nk) - t0):
+                cols.append(tap(ty, tx)[..., ic * bk:(ic + 1) * bk])
+                if ko:
+                    tx += 1
+                    if tx == kw:
+                        tx, ty = 0, ty + 1
+                        if ty == kh:
+                            ty, ic = 0, ic + 1
+                else:
+                    ic += 1
+                    if ic == tpt:
+                        ic, tx = 0, tx + 1
+                        if tx == kw:
+                            tx, ty = 0, ty + 1
+        A = torch.cat(cols, -1).reshape(M, ntap * ct)
+    else:
+        n_walk = ntap
+        over = mut == "partial_tile_overread" and xt is None and not ko
+        if over:          # the walk goes on to the end of the last K tile: the taps behind the window
+            n_walk = -(-(-(-ntap * ct // bk) * bk) // ct)
+        T = torch.stack([tap(*coords(t)) for t in range(n_walk)], 3)                                   # [B, Ho, Wo, taps, Ctot]
+        if ko:
+            T = T.reshape(B, Ho, Wo, kh, kw, ct // bk, bk)
+            T = T.permute(0, 1, 2, 5, 3, 4, 6) if ko == 1 else T.permute(0, 1, 2, 3, 5, 4, 6)
+        A = T.reshape(M, n_walk * ct)[:, :-(-ntap * ct // bk) * bk if over else ntap * ct]
     if xt is not None:
         if mut == "tail_at_input_pixel":          # read at the window's first input pixel instead of the output pixel
             xt = torch.roll(xt, shifts=(pt, pl), dims=(1, 2))
@@ -342,6 +418,9 @@ def contract(c, A, w, mut=None, sk=1):
         bk = bk_of(c)
         k0 = ((K // bk + sk - 1) // sk) * bk
         A, w = torch.cat([A, A[:, k0:k0 + bk]], 1), torch.cat([w, w[:, :, k0:k0 + bk]], 2)
+    if mut == "partial_tile_overread" and K > w.shape[2]:
+        # A runs on to the end of its last K tile (im2col); so does the weight row, into the start of the row behind it (the last row: into row 0)
+        w = torch.cat([w, torch.roll(w, -1, 1)[:, :, :K - w.shape[2]]], 2)
     def mm(a, b):
         if c["op"] == "x3":
             ah, al = split_hi_lo(a)
@@ -393,7 +472,7 @@ def reference(c, i, mut=None, dev="cpu", sk=1, n_split=0):
                 w = i["w3"].permute(0, 2, 3, 1).reshape(1, c["N"], 9 * c["C0"]).to(dev)
                 acc = contract(c, im2col(c, x0, None, None, mut), w, mut, sk)
         else:
-            acc = contract(c, im2col(c, x0, x1, xt, mut), wv[b * S:(b + 1) * S].to(dev), mut, sk)
+            acc = contract(c, im2col(c, x0, x1, xt, mut, sk), wv[b * S:(b + 1) * S].to(dev), mut, sk)
         i["res_cur"] = i["res"][b] if i["res"] is not None else None
         outs.append(epilogue(c, acc, i, mut, n_split))
     return torch.stack(outs, 0)
@@ -614,7 +693,7 @@ def prepare(c, i, dev):
     ldo = c["col0"] + nout + c["ldo_extra"]
     out = guarded_rows(M, nout, ldo, c["col0"], odt, dev, nb)
     ws = guarded_flat(c["ws"] // 4, torch.float32, dev) if c["ws"] else None
-    conv = not (c["ks"] == 1 and c["stride"] == 1 and c["ups"] == 0 and C1 == 0 and c["pad"] == (0, 0, 0, 0))
+    conv = not (c["kh"] == 1 and c["kw"] == 1 and c["stride"] == 1 and c["ups"] == 0 and C1 == 0 and c["pad"] == (0, 0, 0, 0))
     kw = dict(M=M, N=N, K=Kk, C0=C0k, ld0=ld0, src1=src1, C1=C1, ld1=C1, bias=bias, rowvec=rowvec, rows_per_sample=G["rps"], ldv=N if c["rowvec"] else 0,
               residual=res, ldr=nout + 16 if c["res"] else 0, act=c["act"], ldo=ldo, alpha=c["alpha"], act_vec=slopes, korder=c["korder"],
               workspace=ws.view if ws else None, x3=x3, srcx=srcx, Cx=Cx, ldx=Cx, name=c["id"])
@@ -622,7 +701,7 @@ def prepare(c, i, dev):
         if c["ups"] == 2:
             kw.update(Hin=H, Win=W_, Hout=2 * H, Wout=2 * W_, KH=2, KW=2, stride=1, pad_t=1, pad_l=1, ups=2, M=4 * B * H * W_, K=4 * C0, rows_per_sample=4 * H * W_)
         else:
-            kw.update(Hin=H, Win=W_, Hout=G["Ho"], Wout=G["Wo"], KH=c["ks"], KW=c["ks"], stride=c["stride"], pad_t=c["pad"][0], pad_l=c["pad"][1], ups=c["ups"])
+            kw.update(Hin=H, Win=W_, Hout=G["Ho"], Wout=G["Wo"], KH=c["kh"], KW=c["kw"], stride=c["stride"], pad_t=c["pad"][0], pad_l=c["pad"][1], ups=c["ups"])
     else:
         kw.update(Hin=1, Win=M, Hout=1, Wout=M)
     if nb > 1:
@@ -787,7 +866,7 @@ _X(case("geglu-exact-4wave", ["GEGLU exact gate"], _t(128, 128, 4), W=200, N=192
 for _op in ("f16", "f32", "w8", "x3"):
     _o = "16" if _op == "f16" else "f32"
     _X(case(f"{_op}-8wave", [f"{_op} 8-wave tile"], _t(128, 256, 8, direct=1), op=_op, W=6200, N=1024, res=True, out=_o, small=dict(W=300)))
-    _X(case(f"{_op}-4wave-conv", [f"{_op} 4-wave tile"], _t(128, 160, 4, conv=1), op=_op, B=3, H=9, W=9, C0=128, N=144, ks=3, pad=P3, rowvec=True, out=_o,
+    _X(case(f"{_op}-4wave-conv", [f"{_op} 4-wave tile"], _t(128, 160, 4, conv=1, glds=1), op=_op, B=3, H=9, W=9, C0=128, N=144, ks=3, pad=P3, rowvec=True, out=_o,
             korder=0 if _op in ("w8", "x3") else 1))
     _X(case(f"{_op}-sk-frag", [f"{_op} split-K"], _t(128, 320, 8, reduce="frag"), op=_op, W=2048, C0=1536, N=1280, ws=W64, out=_o, sparse="A",
             small=dict(W=300, C0=1024, N=320, ws=4 * MB)))
@@ -804,6 +883,54 @@ _X(case("a8-4wave-160", ["fp8 x fp8 4-wave tile"], _t(128, 160, 4), op="a8", out
 _X(case("a8-conv-c320", ["fp8 x fp8 4-wave tile", "fp8 C = 320 padded to 384"], _t(128, 128, 4, conv=1), op="a8", out="16", B=7, H=9, W=9, C0=320, N=112, ks=3, pad=P3,
         sparse="A", rowvec=True))
 _X(case("a8-sk-frag", ["fp8 x fp8 split-K"], _t(128, 128, 4, reduce="frag"), op="a8", out="16", W=128, C0=2048, N=112, ws=MB, res=True))
+# ---- windows: the geometries the metric towers and front-ends launch (TOWER_WINDOWS below).  Dense operands in +-{1, 2, 3} and fp32 output: every
+# tap, channel and border pixel is live in every output row.  cp8: 3 real channels stored in 8 -- non-zero activations in the pad channels, zero weight
+# columns.  Shapes are the smallest that cross every edge: odd and even extents on different axes, several samples, N ragged where the plan allows
+_CP8 = dict(C0=8, creal=3)
+P5, P7 = (2, 2, 2, 2), (3, 3, 3, 3)          # the "same" padding of a 5x5 and of a 7x7 window, as P3 is that of a 3x3
+_X(case("win-7x7-s2-cp8", ["window 7x7 s2 p3 on the register loop"], _t(128, 64, 4, glds=0, conv=1, splitk=1), op="f32", B=2, H=13, W=10, N=64, ks=7, stride=2,
+        pad=P7, act=RL, **_CP8))                                                     # K = 392: four taps per K tile, 8 of 32 positions live in the last one
+_X(case("win-11x11-s4-cp8", ["window 11x11 s4 p2 on the register loop"], _t(128, 64, 4, glds=0, conv=1, splitk=1), op="f32", B=2, H=23, W=19, N=64, ks=11, stride=4,
+        pad=P5, act=RL, bias=False, **_CP8))                                          # (H + 2p - k) % s != 0 on both axes: trailing rows / columns unread
+for _op in ("f32", "bf16"):          # (VGG16's and the IResNet's first layer; not in the issue's list)
+    _X(case(f"win-3x3-cp8-{_op}", ["window 3x3 p1 on the register loop (3 channels stored in 8)"], _t(128, 64, 4, glds=0, conv=1, splitk=1), op=_op, B=2, H=7, W=6, N=64,
+            ks=3, pad=P3, act=RL, **_CP8))
+_X(case("win-5x5-c64", ["window 5x5 p2 direct-to-LDS"], _t(128, 128, 4, glds=1, conv=1, splitk=1), op="f32", B=2, H=9, W=7, C0=64, N=96, ks=5, pad=P5))
+for _op in ("f32", "bf16"):
+    # odd extent 9 -> 5 uses the bottom pad row; even extent 8 -> 4 never reads the right pad column
+    _X(case(f"win-3x3-s2-p1-{_op}", ["3x3 s2 symmetric pad"], _t(128, 128, 4, glds=1, conv=1, splitk=1), op=_op, B=3, H=9, W=8, C0=64, N=100, ks=3, stride=2, pad=P3))
+    _X(case(f"win-1x1-s2-{_op}", ["1x1 s2 with conv addressing"], _t(128, 128, 4, glds=1, conv=1, splitk=1), op=_op, B=3, H=9, W=8, C0=64, N=128, ks=1, stride=2,
+            **(dict(res=True, act=AR) if _op == "bf16" else {})))                     # (bf16: the bottleneck's join)
+    _X(case(f"win-patch14-{_op}", ["patch window, stride = window"], _t(128, 64, 4, glds=0, conv=1, splitk=1), op=_op, B=2, H=28, W=42, N=64, ks=14, stride=14,
+            bias=False, **_CP8))                                                      # M = 12 < BM
+# K = 8192 on the register loop, M = 4: once without a workspace, once with one (guarded).  pick_splitk's cost model prices 2 M N K flops against
+# the 3 us of a reduce pass, so with M = 4 rows it keeps splitk = 1 at any workspace size: that plan is what the second case asserts and checks
+_X(case("win-patch32-f32", ["patch window, long K on the register loop"], _t(128, 64, 4, glds=0, conv=1, splitk=1), op="f32", B=2, H=64, W=32, N=64, ks=32, stride=32,
+        bias=False, **_CP8))
+_X(case("win-patch32-f32-ws", ["patch window, long K on the register loop"], _t(128, 64, 4, glds=0, conv=1, splitk=1), op="f32", B=2, H=64, W=32, N=64, ks=32, stride=32,
+        bias=False, ws=MB, **_CP8))
+_X(case("win-patch32-bf16", ["patch window, long K on the register loop"], _t(128, 64, 4, glds=0, conv=1, splitk=1), B=2, H=64, W=32, N=64, ks=32, stride=32, bias=False,
+        **_CP8))
+# the fp32 CLIP towers store the 3 channels in 4 -- a tap is ONE 16-byte vector, eight taps per K tile (not in the issue's list: encoders.py, fidscore.py)
+_X(case("win-patch14-f32-cp4", ["patch window, 3 channels stored in 4 (one fp32 vector per tap)"], _t(128, 64, 4, glds=0, conv=1, splitk=1), op="f32", B=2, H=28, W=42,
+        C0=4, creal=3, N=64, ks=14, stride=14, bias=False))                           # K = 784: half of the last K tile live
+_X(case("win-patch32-f32-cp4", ["patch window, 3 channels stored in 4 (one fp32 vector per tap)"], _t(128, 64, 4, glds=0, conv=1, splitk=1), op="f32", B=2, H=64, W=32,
+        C0=4, creal=3, N=64, ks=32, stride=32, bias=False))
+_X(case("win-1x7-s2-regs", ["non-square window, pad_t != pad_l"], _t(128, 64, 4, glds=0, conv=1, splitk=1), op="f32", B=2, H=9, W=12, C0=8, N=64, kh=1, kw=7, stride=2,
+        pad=(0, 3, 0, 3)))
+_X(case("win-5x3-lds", ["non-square window, pad_t != pad_l"], _t(128, 128, 4, glds=1, conv=1, splitk=1), B=2, H=9, W=11, C0=64, N=100, kh=5, kw=3, pad=(2, 1, 2, 1)))
+# split-K over a non-square window: 30 K tiles in three slices of 10, two tiles per tap -- the slices start at taps 0, 5 and 10 (korder 0) and at
+# taps 0, 10 and 5 (korder 1), inside window rows 1 and 3 (a multiple of KW = 3 would be a row's first tap: the GPU test asserts it from the plan)
+_X(case("win-5x3-lds-k1", ["non-square window under korder 1"], _t(128, 128, 4, glds=1, conv=1, splitk=3, reduce="stripe8"), B=1, H=8, W=8, C0=128, N=112, kh=5, kw=3, pad=(2, 1, 2, 1),
+        korder=1, ws=MB))
+_X(case("win-5x3-lds-sk", ["non-square window under split-K"], _t(128, 128, 4, glds=1, conv=1, splitk=3, reduce="stripe8"), B=1, H=8, W=8, C0=128, N=112, kh=5, kw=3, pad=(2, 1, 2, 1), ws=MB))
+# the packed row descriptor sample:12 | oy:10 | ox:10 of the direct-to-LDS loop: the last shape it takes and the first that goes through registers
+_X(case("win-hout-1024", ["packed row descriptor at its limit"], _t(128, 64, 4, glds=1, conv=1), H=1024, W=1, ks=3, pad=P3))
+_X(case("win-hout-1025", ["packed row descriptor at its limit"], _t(128, 64, 4, glds=0, conv=1), H=1025, W=1, ks=3, pad=P3))
+_X(case("win-wout-1024", ["packed row descriptor at its limit"], _t(128, 64, 4, glds=1, conv=1), H=1, W=1024, ks=3, pad=P3))          # (the ox field: not in the issue's list)
+_X(case("win-wout-1025", ["packed row descriptor at its limit"], _t(128, 64, 4, glds=0, conv=1), H=1, W=1025, ks=3, pad=P3))
+_X(case("win-samples-4094", ["packed sample field at its limit"], _t(128, 64, 4, glds=1, conv=1), B=4094, ks=3, pad=P3))
+_X(case("win-samples-4095", ["packed sample field at its limit"], _t(128, 64, 4, glds=0, conv=1), B=4095, ks=3, pad=P3))
 del _X
 
 BY_ID = {c["id"]: c for c in CASES}
@@ -840,3 +967,77 @@ CELLS = ("tile 256x320", "tile 256x256", "tile 128x320", "tile 128x256", "tile 1
          "edge ragged M", "edge ragged N", "edge pitched column slice", "edge tile spans a sample boundary") + tuple(
     f"{op} {what}" for op in ("f16", "f32", "w8", "x3") for what in ("8-wave tile", "4-wave tile", "split-K")) + (
     "fp8 x fp8 8-wave tile", "fp8 x fp8 4-wave tile", "fp8 x fp8 split-K")
+CELLS += ("window 7x7 s2 p3 on the register loop", "window 11x11 s4 p2 on the register loop", "window 3x3 p1 on the register loop (3 channels stored in 8)",
+          "window 5x5 p2 direct-to-LDS", "3x3 s2 symmetric pad", "1x1 s2 with conv addressing", "patch window, stride = window",
+          "patch window, 3 channels stored in 4 (one fp32 vector per tap)", "patch window, long K on the register loop", "non-square window, pad_t != pad_l",
+          "non-square window under korder 1", "non-square window under split-K", "packed row descriptor at its limit", "packed sample field at its limit")
+
+
+# ------------------------------------------------------------------------------------------------ the window cases
+def is_window_case(c):
+    return c["id"].startswith("win-")
+
+
+WINDOW_CASES = [c for c in CASES if is_window_case(c)]
+
+
+def live_k(c):
+    """True where column k of a dense window case must carry a non-zero product in some row: its tap reaches into the image for some output pixel
+    and its channel is a real one (not a zero weight column of a channel-padded input).  korder 0 / 1 only."""
+    G = geom(c)
+    reach = lambda k, pad, n_in, n_out: any(0 <= o * c["stride"] - pad + k < n_in for o in range(n_out))
+    tap = torch.tensor([reach(t // c["kw"], c["pad"][0], c["H"], G["Ho"]) and reach(t % c["kw"], c["pad"][1], c["W"], G["Wo"]) for t in range(G["taps"])])
+    ch = torch.arange(G["ctot"]) < (c["creal"] or G["ctot"])
+    m = tap[:, None] & ch[None, :]
+    if c["korder"] == 1:
+        bk = bk_of(c)
+        m = m.reshape(G["taps"], G["ctot"] // bk, bk).permute(1, 0, 2)
+    assert c["korder"] < 2
+    return m.reshape(-1)
+
+
+def window_mutant_applies(m, c, sk=1):
+    """whether slip `m` of the window addressing can show in window case c at all: the geometry has what the slip confuses"""
+    G = geom(c)
+    kh, kw, s = c["kh"], c["kw"], c["stride"]
+    pt, pl = c["pad"][0], c["pad"][1]
+    if m == "kh_kw_swapped":
+        return kh != kw
+    if m == "pad_t_l_swapped":
+        return pt != pl
+    if m == "stride_rows_only":
+        return s > 1 and G["Wo"] > 1
+    if m == "border_clamped":          # some tap of some output pixel lies outside the image
+        return pt > 0 or pl > 0 or (G["Ho"] - 1) * s - pt + kh > c["H"] or (G["Wo"] - 1) * s - pl + kw > c["W"]
+    if m == "cin_pad_ignored":
+        return c["creal"] > 0
+    if m == "partial_tile_overread":
+        return G["K"] % bk_of(c) != 0
+    if m == "slice_start_tap":          # some slice but the first starts at a tap that KH and KW decode differently
+        if sk < 2 or G["ctot"] % bk_of(c) or c["korder"] > 1:
+            return False
+        taps = [tap_of_tile(c, t0) for t0 in slice_starts(c, sk)[0][1:]]
+        return any((t // kh, t % kh) != (t // kw, t % kw) for t in taps)
+    raise KeyError(m)
+
+
+# who launches which window: (who, KH, KW, stride, pad, stored input channels, operand type) -> the case that pins it.  tests/test_gemm_exact_cpu.py walks
+# reface_amd.params.lpips_plan against the rows; the ResNet / IResNet / patch rows restate the source lines named behind them
+TOWER_WINDOWS = {
+    ("Hopenet ResNet-50 conv1", 7, 7, 2, 3, 8, "f32"): "win-7x7-s2-cp8",                     # posescore.py: _conv(self.x, "conv1.weight", 64, ..., ksize=7, stride=2, cin_pad=self.CP)
+    ("Deep3DFaceRecon ResNet-50 conv1", 7, 7, 2, 3, 8, "f32"): "win-7x7-s2-cp8",             # exprscore.py: _conv(self.x, "backbone.conv1.weight", 64, ..., ksize=7, stride=2, cin_pad=self.CP)
+    ("BiSeNet ResNet-18 conv1", 7, 7, 2, 3, 8, "f32"): "win-7x7-s2-cp8",                     # parsing.py: _conv(x, "cp.resnet.conv1.weight", 64, ..., ksize=7, stride=2, cin_pad=self.CP)
+    ("LPIPS AlexNet features.0", 11, 11, 4, 2, 8, "f32"): "win-11x11-s4-cp8",                # lpips.py: pack_conv_weight(..., cin_pad=CP if first else None), lpips_plan("alex")[0]
+    ("LPIPS AlexNet features.3", 5, 5, 1, 2, 64, "f32"): "win-5x5-c64",
+    ("LPIPS AlexNet features.6-10 / VGG16 features.2-28", 3, 3, 1, 1, 64, "f32"): "f32-4wave-conv",
+    ("LPIPS VGG16 features.0", 3, 3, 1, 1, 8, "f32"): "win-3x3-cp8-f32",
+    ("ArcFace IResNet input_layer.0", 3, 3, 1, 1, 8, "bf16"): "win-3x3-cp8-bf16",            # encoders.py: _conv(x, "input_layer.0.weight", 64, ..., cin_pad=self.CP)
+    ("ResNet stage entry conv (fp32 towers)", 3, 3, 2, 1, 64, "f32"): "win-3x3-s2-p1-f32",   # posescore.py / exprscore.py: conv2 of a stage's first block, ksize=3, stride=stride; parsing.py: conv1
+    ("IResNet stage entry res_layer.3 (ArcFace)", 3, 3, 2, 1, 64, "bf16"): "win-3x3-s2-p1-bf16",          # encoders.py: _conv(r1, "res_layer.3.weight", depth, stride=stride, ...)
+    ("ResNet downsample.0 (fp32 towers)", 1, 1, 2, 0, 64, "f32"): "win-1x1-s2-f32",          # posescore.py / exprscore.py / parsing.py: "downsample.0.weight", ksize=1, stride=stride
+    ("IResNet shortcut_layer.0 (ArcFace)", 1, 1, 2, 0, 64, "bf16"): "win-1x1-s2-bf16",       # encoders.py: _conv(x, "shortcut_layer.0.weight", depth, stride=stride, ksize=1, ...)
+    ("CLIP ViT-L/14 patch embedding", 14, 14, 14, 0, 8, "bf16"): "win-patch14-bf16",          # encoders.py / fidscore.py: ksize=P, stride=P, pad=(0, 0), CP = 8 for 16-bit operands
+    ("CLIP ViT-L/14 patch embedding", 14, 14, 14, 0, 4, "f32"): "win-patch14-f32-cp4",       # ... CP = 4 for fp32 operands (one 16-byte pixel)
+    ("CLIP ViT-B/32 patch embedding (FID)", 32, 32, 32, 0, 4, "f32"): "win-patch32-f32-cp4",  # fidscore.py: ksize=P, stride=P, pad=(0, 0), self.CP = 4 if dtype == F32 else 8
+    ("CLIP ViT-B/32 patch embedding (FID)", 32, 32, 32, 0, 8, "bf16"): "win-patch32-bf16",
+}

@@ -4,7 +4,11 @@
   b. the reference restatement equals torch's own fp64 conv2d / linear on random real-valued data within 1e-12, for every loop feature;
   c. every slip a kernel could make, written as a deliberately wrong variant of the *reference*, changes an output of EVERY case it applies to
      (a mutant that no case distinguishes fails by name);
-  d. the plan every case names is the plan rf_conv_gemm_plan3 reports -- a host-only query, so a dispatch retune shows up without a GPU.
+  d. the plan every case names is the plan rf_conv_gemm_plan3 reports -- a host-only query, so a dispatch retune shows up without a GPU;
+  e. the window cases (KH x KW, stride, pad_t / pad_l, channel-padded inputs, the limits of the packed row descriptor): their reference equals
+     torch's fp64 conv2d on the case's own integers, and the window slips change a case exactly where its geometry has what they confuse --
+     no slip idle, no case vacuous;
+  f. ops.pack_conv_weight writes the [N, K] layout the reference multiplies, and every window a tower launches has a case (TOWER_WINDOWS).
 No kernel runs."""
 import pytest
 import torch
@@ -41,7 +45,7 @@ def static_bound(c):
         per = 3.0 * 6.0
     else:
         per = 9.0
-    taps = 9 if c["ups"] == 2 else c["ks"] ** 2
+    taps = 9 if c["ups"] == 2 else c["kh"] * c["kw"]
     k = taps * (c["C0"] + c["C1"]) + c["Cx"]
     return (abs(c["alpha"]) * k * per + 66 + 7 + 15 + 80) * (2.0 if c["act"] == ops.ACT_PRELU else 1.0) / (min(1.0, c["alpha"]) * (0.25 if c["act"] == ops.ACT_PRELU else 1.0))
 
@@ -89,7 +93,9 @@ def test_sparse_seeds_cover_every_k():
         if o is None and c["id"].endswith("-W"):
             o = R.small_of(R.BY_ID[c["id"][:-2] + "-A"])
         cov = R.k_coverage(c, R.make_inputs(c))
-        if o is not None:
+        if R.is_window_case(c):          # dense: exactly the k whose tap reaches the image and whose channel is a real one (the rest is zero by construction)
+            assert torch.equal(cov, R.live_k(c)) and bool(cov.any()), c["id"]
+        elif o is not None:
             cov = cov | R.k_coverage(o, R.make_inputs(o))
             assert bool(cov.all()), (c["id"], int((~cov).sum()), cov.numel())
         else:
@@ -199,9 +205,22 @@ def test_reference_epilogues_equal_torch_fp64():
 
 
 # ------------------------------------------------------------------------------------------------ c. mutants
+def _sk(c):
+    """the split-K factor a mutant is run at: the one the case froze from the plan, else 2 for a case with a workspace"""
+    return c["expect"].get("splitk", 2) if c["ws"] else 1
+
+
 def _applies(m, c):
+    if m in R.WINDOW_MUTANTS:          # the window slips answer to the window cases (two-sided check below)
+        return R.is_window_case(c) and R.window_mutant_applies(m, c, _sk(c))
     conv3 = c["ks"] == 3 or c["ups"] == 2
-    return {"drop_last_k": True, "double_k_tile": bool(c["ws"]), "tap_transposed": conv3,
+    if R.is_window_case(c) and m in ("drop_last_k", "tap_transposed", "halo_from_adjacent_row"):
+        # dense window cases at extreme shapes: the slip must have something to confuse -- a live last k (not a zero weight column of a padded
+        # channel, not a tap that only ever meets padding), two different off-diagonal taps inside the image, a neighbouring image row
+        live = R.live_k(c)
+        tt = c["H"] > 1 and c["W"] > 1 and c["kh"] == c["kw"] and c["kh"] > 1
+        return {"drop_last_k": bool(live[-1]), "tap_transposed": tt, "halo_from_adjacent_row": conv3 and c["pad"][1] > 0 and c["H"] > 1}[m]
+    return {"drop_last_k": True, "double_k_tile": _sk(c) > 1, "tap_transposed": conv3,
             "halo_from_adjacent_row": conv3 and (c["ups"] == 2 or c["pad"][1] > 0), "pad_top_bottom_swapped": c["pad"][0] != c["pad"][2],
             "phase_swapped": c["ups"] == 2, "phase00_padding": c["ups"] == 2, "concat_swapped": c["C1"] > 0, "tail_at_input_pixel": c["Cx"] > 0,
             "korder_confused": c["korder"] > 0 and c["ups"] != 2, "rowvec_neighbour": c["rowvec"] and c["B"] > 1, "residual_row_plus_1": c["res"],
@@ -246,7 +265,7 @@ def test_mutant_is_told_apart_by_every_case_it_applies_to(m):
             wrong[:, :bm, :bn], wrong[:, :bm, bn:2 * bn] = ref[:, :bm, bn:2 * bn], ref[:, :bm, :bn]
         else:
             n_split = 256 if c["expect"].get("gemm_kernels") == 2 else 0          # (the scaled-down N split: whole 256-wide tiles, then the tail)
-            wrong = R.reference(c, i, m, sk=2 if c["ws"] else 1, n_split=n_split)
+            wrong = R.reference(c, i, m, sk=_sk(c), n_split=n_split)
         if not _differs(c, wrong, ref):
             missed.append(c["id"])
     assert not missed, f"mutant {m} is not told apart by: {missed}"
@@ -276,3 +295,121 @@ def test_every_cell_has_a_case_and_plan3_is_exported():
     assert _lib.load().rf_version() >= 104 and "rf_conv_gemm_plan3" in _lib.EXPORTS
     have = {cell for c in R.CASES for cell in c["cells"]}
     assert not [cell for cell in R.CELLS if cell not in have]
+
+
+# ------------------------------------------------------------------------------------------------ e. the window cases
+WIN = R.WINDOW_CASES
+WIN_IDS = [c["id"] for c in WIN]
+
+
+@pytest.fixture(scope="module")
+def win_refs():
+    """inputs and fp64 reference of every window case, computed once"""
+    return {c["id"]: _prepared(c) for c in WIN}
+
+
+def _w4(c, i):
+    """the [N, Cin, KH, KW] filter a case's [N, K] weight matrix is the packing of"""
+    N, kh, kw, ct = c["N"], c["kh"], c["kw"], c["C0"]
+    w = i["w"][0]
+    if c["korder"] == 1:
+        bk = R.bk_of(c)
+        w = w.reshape(N, ct // bk, kh * kw, bk).permute(0, 2, 1, 3)
+    assert c["korder"] < 2
+    return w.reshape(N, kh, kw, ct).permute(0, 3, 1, 2).contiguous()
+
+
+@pytest.mark.parametrize("c", WIN, ids=WIN_IDS)
+def test_window_reference_equals_conv2d_fp64(c, win_refs):
+    """the KH x KW / stride / pad_t, pad_l reference against torch's own conv2d in float64 on the case's own integer operands: equal, not close"""
+    i, ref = win_refs[c["id"]]
+    pt, pl, pb, pr = c["pad"]
+    x = F.pad(i["x0"].permute(0, 3, 1, 2), (pl, pr, pt, pb))
+    y = F.conv2d(x, _w4(c, i), stride=c["stride"]).permute(0, 2, 3, 1).reshape(-1, c["N"])
+    assert y.shape[0] == R.geom(c)["M"]
+    if i["bias"] is not None:
+        y = y + i["bias"][None]
+    if c["act"] == ops.ACT_ADD_RELU:
+        y = F.relu(y + i["res"][0])
+    else:
+        assert c["act"] in (ops.ACT_NONE, ops.ACT_RELU) and not c["res"]
+        y = F.relu(y) if c["act"] == ops.ACT_RELU else y
+    assert torch.equal(ref[0], y)
+    R.assert_exact(c, i, ref)                                      # all partial sums below 2^24
+    assert R.magnitude_bound(c, i)[0] <= 9 * R.geom(c)["K"] + 7 + 15 < R.EXACT_LIMIT
+
+
+def test_window_mutants_two_sided(win_refs):
+    """every window slip changes an output of some window case, every window case is changed by some window slip -- and a slip changes a case exactly
+    where the case's geometry has what the slip confuses (gemm_exact_refs.window_mutant_applies): no case is vacuous, no mutant is idle"""
+    changed = set()
+    for c in WIN:
+        i, ref = win_refs[c["id"]]
+        for m in R.WINDOW_MUTANTS:
+            if _differs(c, R.reference(c, i, m, sk=_sk(c)), ref):
+                changed.add((m, c["id"]))
+    applies = {(m, c["id"]) for c in WIN for m in R.WINDOW_MUTANTS if R.window_mutant_applies(m, c, _sk(c))}
+    assert changed == applies, (sorted(changed - applies), sorted(applies - changed))
+    idle = [m for m in R.WINDOW_MUTANTS if not any(k[0] == m for k in changed)]
+    vacuous = [c["id"] for c in WIN if not any(k[1] == c["id"] for k in changed)]
+    assert not idle and not vacuous, (idle, vacuous)
+    for m in R.WINDOW_MUTANTS:
+        print(f"[gemm_exact] window mutant {m}: changes {sorted(k[1] for k in changed if k[0] == m)}")
+
+
+def test_split_slices_start_inside_the_window():
+    """the split-K cases of the non-square window: some slice starts at a tap that is not the first of a window row"""
+    for cid in ("win-5x3-lds-k1", "win-5x3-lds-sk"):
+        c = R.BY_ID[cid]
+        starts, nk = R.slice_starts(c, c["expect"]["splitk"])
+        assert nk == 30 and any(R.tap_of_tile(c, t0) % c["kw"] for t0 in starts[1:]), (cid, starts)
+
+
+# ------------------------------------------------------------------------------------------------ f. host packing and the tower table
+@pytest.mark.parametrize("c", WIN, ids=WIN_IDS)
+def test_pack_conv_weight_gives_the_layout_the_reference_multiplies(c, win_refs):
+    i, _ = win_refs[c["id"]]
+    w4 = _w4(c, i)
+    cr = c["creal"] or c["C0"]
+    assert not bool(w4[:, cr:].any())
+    got = ops.pack_conv_weight(w4[:, :cr].float(), R.TDT[c["op"]], cin_pad=c["C0"] if c["creal"] else None, korder=c["korder"])
+    assert got.dtype == R.TDT[c["op"]] and got.is_contiguous() and torch.equal(got.double(), i["w"][0])
+
+
+@pytest.mark.parametrize("kh,kw", [(1, 1), (3, 3), (5, 5), (7, 7), (11, 11), (14, 14), (5, 3), (1, 7)])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_pack_conv_weight_index_formula(kh, kw, dtype):
+    """k = (ky KW + kx) Cin_pad + c (korder 0), ((c / BK) KH KW + tap) BK + c % BK (korder 1), ((ky (Cin_pad / BK) + c / BK) KW + kx) BK + c % BK (korder 2),
+    restated as index arithmetic; pad channels are zero columns"""
+    bk = 32 if dtype == torch.float32 else 64
+    for ci, cp, korders in ((3, 8, (0,)), (3, 4, (0,)), (bk + 3, 2 * bk, (0, 1, 2)), (2 * bk, None, (0, 1, 2))):
+        n = 5
+        w = (torch.arange(n * ci * kh * kw) % 251 - 125).float().reshape(n, ci, kh, kw)          # integers bf16 holds exactly, no two neighbours alike
+        cpad = cp or ci
+        cc, ky, kx = torch.meshgrid(torch.arange(ci), torch.arange(kh), torch.arange(kw), indexing="ij")
+        for ko in korders:
+            k = {0: (ky * kw + kx) * cpad + cc, 1: ((cc // bk) * kh * kw + ky * kw + kx) * bk + cc % bk, 2: ((ky * (cpad // bk) + cc // bk) * kw + kx) * bk + cc % bk}[ko]
+            want = torch.zeros((n, kh * kw * cpad))
+            want[:, k.reshape(-1)] = w.reshape(n, -1)
+            got = ops.pack_conv_weight(w, dtype, cin_pad=cp, korder=ko)
+            assert got.shape == want.shape and got.dtype == dtype and torch.equal(got.float(), want), (kh, kw, ci, cp, ko)
+
+
+def test_tower_windows_table_names_a_case_for_every_launched_window():
+    from reface_amd.params import lpips_plan
+    rows = {k[1:]: v for k, v in R.TOWER_WINDOWS.items()}
+    for net in ("alex", "vgg"):
+        first = True
+        for p in lpips_plan(net):
+            if p[0] != "conv":
+                continue
+            _, _, cin, _, k, s, pad = p
+            stored = 8 if first else 64          # lpips.py: cin_pad=CP if first else None; every later layer has a multiple of 64 channels
+            assert first or cin % 64 == 0
+            assert (k, k, s, pad, stored, "f32") in rows, (net, p)
+            first = False
+    for (who, kh, kw, s, pad, stored, op), cid in R.TOWER_WINDOWS.items():
+        c = R.BY_ID[cid]
+        assert (c["kh"], c["kw"], c["stride"], c["pad"][0], c["pad"][1], c["op"]) == (kh, kw, s, pad, pad, op), (who, cid)
+        assert (c["C0"] == stored if stored < 64 else c["C0"] % 64 == 0) and c["C1"] == 0 and c["ups"] == 0, (who, cid)
+        assert c["expect"]["glds"] == (0 if stored < 64 else 1) and c["expect"]["conv"] == 1, (who, cid)

@@ -46,6 +46,11 @@ def _run(c, note=""):
     lost = R.plan_matches(pl, c["expect"])
     assert not lost, f"the cells {c['cells']} lost their case {c['id']}: {lost}"
     assert (pl["splitk"] > 1) == ("reduce" in c["expect"]), (c["id"], pl)
+    if R.is_window_case(c) and c["kh"] != c["kw"] and pl["splitk"] > 1:
+        # a split non-square window: by the plan's own split some slice starts inside a window row, at a tap KH and KW decode differently
+        starts, nk = R.slice_starts(c, pl["splitk"])
+        assert nk == -(-G["K"] // R.bk_of(c)) and any(R.tap_of_tile(c, t0) % c["kw"] for t0 in starts[1:]), (c["id"], starts)
+        assert R.window_mutant_applies("slice_start_tap", c, pl["splitk"]), c["id"]
     ref = R.reference(c, i, dev=DEV)
     if c["ln"] == "prod":
         ref = R.steer_stripe_means(c, i, ref.cpu(), pl["wave_cols"]).to(DEV)
