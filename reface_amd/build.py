@@ -20,10 +20,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # 10 of the ~86 VALU instructions per 64 x 32 unit of the VALU-bound d = 40 kernel.  Scores are finite (masked keys are -inf, never NaN): -0.35 % per batch at 512x512,
 # -0.6 % at 768x768, every attention test unchanged (profiles/r06e_attention_no_nan_quieting.txt).
 EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"]}
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(os.path.dirname(HERE), "include", "reface_hip.h")]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "check.h"), os.path.join(os.path.dirname(HERE), "include", "reface_hip.h")]
 # further files a unit includes (part of its content key): gemm_f16.hip is gemm.hip's templates instantiated for fp16 operands
+# gemm_plan.h: rf_conv_gemm's planner, host-only C++ that gemm.hip launches from and a host compiler builds into tests/gemm_plan_host_main.cpp
 # pil_u8.h: PIL's sampler / clip / packed store shared by the units that reproduce PIL's bytes; cv_u8.h: cv2's u8 INTER_LINEAR taps likewise
-UNIT_DEPS = {"gemm_f16.hip": [os.path.join(CSRC, "gemm.hip")], "pasteback.hip": [os.path.join(CSRC, "pil_u8.h")], "align.hip": [os.path.join(CSRC, "pil_u8.h")],
+UNIT_DEPS = {"gemm.hip": [os.path.join(CSRC, "gemm_plan.h")], "gemm_f16.hip": [os.path.join(CSRC, "gemm.hip"), os.path.join(CSRC, "gemm_plan.h")],
+             "pasteback.hip": [os.path.join(CSRC, "pil_u8.h")], "align.hip": [os.path.join(CSRC, "pil_u8.h")],
              "video_prep.hip": [os.path.join(CSRC, "pil_u8.h")], "elementwise.hip": [os.path.join(CSRC, "cv_u8.h")],
              "idscore.hip": [os.path.join(CSRC, "cv_u8.h")], "expr.hip": [os.path.join(CSRC, "pil_u8.h")],
              "fid.hip": [os.path.join(CSRC, "pil_u8.h")],

@@ -20,19 +20,11 @@ typedef _Float16 f16_t;    // storage type of fp16 (IEEE binary16) values -- a t
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 typedef uint8_t fp8_t;     // storage type of OCP e4m3fn values (fp8 activations / weights of the MX-scaled MFMA path)
 
+#include "check.h"          // rf::set_error, RF_CHECK
+
 namespace rf {
 
-void set_error(const char* fmt, ...);
-
 // The library reads NO environment variable: a stray variable in a user's shell cannot change its results.
-
-#define RF_CHECK(cond, ...)                                     \
-    do {                                                        \
-        if (!(cond)) {                                          \
-            rf::set_error(__VA_ARGS__);                         \
-            return 1;                                           \
-        }                                                       \
-    } while (0)
 
 #define RF_LAUNCH_CHECK(name)                                               \
     do {                                                                    \

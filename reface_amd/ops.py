@@ -658,37 +658,34 @@ def groupnorm(x, gamma, beta, out, partial, *, eps, silu, split=False, name="gro
 
 def gemm_plan(launch):
     """(rows, columns of the block that finishes an output tile, split-K factor) rf_conv_gemm will use for this prepared launch."""
-    lib = _lib.load()
-    bm, bn, sk = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-    _lib.check(lib.rf_conv_gemm_plan(C.byref(launch.keep[0]), C.byref(bm), C.byref(bn), C.byref(sk)), launch.name + ".plan")
-    return bm.value, bn.value, sk.value
+    pl = gemm_plan3(launch, ".plan")
+    return pl["stat_rows"], pl["stat_cols"], pl["splitk"]
+
+
+PLAN2_KEYS = ("stat_rows", "stat_cols", "splitk", "bm", "bn", "wave_cols", "direct", "frag", "gemm_kernels")
 
 
 def gemm_plan2(launch):
     """The whole tile plan of a prepared rf_conv_gemm launch: dict(stat_rows, stat_cols, splitk, bm, bn, wave_cols, direct, frag, gemm_kernels); raises
     RefaceHipError when the library rejects the descriptor (e.g. LayerNorm folding asked of a launch that cannot carry it)."""
-    lib = _lib.load()
-    info = (C.c_int32 * 8)()
-    _lib.check(lib.rf_conv_gemm_plan2(C.byref(launch.keep[0]), info), launch.name + ".plan2")
-    pl = dict(zip(("stat_rows", "stat_cols", "splitk", "bm", "bn", "wave_cols", "direct", "frag"), (int(v) for v in info)))
-    # eighth word: bit 0 = split-K through fragment-ordered slabs, bit 1 = the call runs as TWO GEMM kernels (tail-round split along N)
-    pl["gemm_kernels"] = 2 if pl["frag"] & 2 else 1
-    pl["frag"] &= 1
-    return pl
+    pl = gemm_plan3(launch, ".plan2")
+    return {k: pl[k] for k in PLAN2_KEYS}
 
 
 REDUCE_KINDS = ("none", "stripe8", "stripe32", "frag")
 
 
-def gemm_plan3(launch):
+def gemm_plan3(launch, what=".plan3"):
     """Everything that names the kernels of a prepared rf_conv_gemm launch (rf_conv_gemm_plan3, no launch): gemm_plan2's dict plus waves (4 | 8), stages
     (2, or 4 for the ring), hx, glds, conv, ln_role (0 none, 1 producer, 2 consumer), pm, pn, reduce (one of REDUCE_KINDS), tiles_m, tiles_n and, for a
-    two-kernel N split, tail = (BM, BN, waves, direct) of the second kernel and split_n = the columns of the first (else None / 0)."""
+    two-kernel N split, tail = (BM, BN, waves, direct) of the second kernel and split_n = the columns of the first (else None / 0).  The one place
+    that decodes the words of include/reface_hip.h: gemm_plan and gemm_plan2 are views of this dict (`what` names the query in a rejection)."""
     lib = _lib.load()
     info = (C.c_int32 * 24)()
-    _lib.check(lib.rf_conv_gemm_plan3(C.byref(launch.keep[0]), info), launch.name + ".plan3")
+    _lib.check(lib.rf_conv_gemm_plan3(C.byref(launch.keep[0]), info), launch.name + what)
     v = [int(x) for x in info]
-    pl = dict(zip(("stat_rows", "stat_cols", "splitk", "bm", "bn", "wave_cols", "direct", "frag"), v[:8]))
+    pl = dict(zip(PLAN2_KEYS[:8], v[:8]))
+    # eighth word: bit 0 = split-K through fragment-ordered slabs, bit 1 = the call runs as TWO GEMM kernels (tail-round split along N)
     pl["gemm_kernels"] = 2 if pl["frag"] & 2 else 1
     pl["frag"] &= 1
     pl.update(waves=v[8], stages=v[9], hx=v[10], glds=v[11], conv=v[12], ln_role=v[13], pm=v[14], pn=v[15], reduce=REDUCE_KINDS[v[16]],

@@ -9,6 +9,11 @@ needed to regenerate the weights); no reference source is copied.
 
 Usage:  python tools/gen_golden.py [group ...]     (groups: schedule unet_ops unet_small unet_full
                                                     ddim vae arcface clip e2e bisenet align idscore pose expr fid lpips)
+
+One group records this project's own library instead of the reference and is run by name only:
+        REFACE_HIP_LIB=<libreface_hip.so of the commit to record> python tools/gen_golden.py gemm_plans <commit>
+writes tests/golden/gemm_plans.json, the answers of rf_conv_gemm_plan3 over the sweep of tests/gemm_plan_sweep.py.  It exists to pin the planner
+ACROSS a change of its code: record at the commit before the change, never from the code the table is meant to check.
 """
 import os
 import sys
@@ -1349,11 +1354,23 @@ def gen_lpips():
          folder_value_f32=np.float64(LP.score_host(fv32)["lpips_value"]), e_ref=np.float64(e_ref), e_ref_near=np.float64(e_near), seed=LP.SEED, **out)
 
 
+def gen_gemm_plans(recorded_from="unknown"):
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    import gemm_plan_sweep
+    from reface_amd import _lib
+    n, nmsg, size = gemm_plan_sweep.record(recorded_from)
+    print(f"  wrote {gemm_plan_sweep.GOLDEN}: {n} descriptors, {nmsg} distinct rejections, {size / 1024:.1f} KiB, asked of {_lib.LIB_PATH} ({recorded_from})")
+
+
 GROUPS = dict(ddim_full=gen_ddim_full, unet_keys=gen_unet_keys, plms=gen_plms, schedule=gen_schedule, unet_ops=gen_unet_ops, unet_small=gen_unet_small, unet_full=gen_unet_full,
               ddim=gen_ddim, vae=gen_vae, arcface=gen_arcface, clip=gen_clip, e2e=gen_e2e,
               bisenet=gen_bisenet, align=gen_align, idscore=gen_idscore, pose=gen_pose, expr=gen_expr, fid=gen_fid, lpips=gen_lpips)
 
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["gemm_plans"]:          # (by name only, with the commit whose library is loaded: see the module's help text)
+        print("[gemm_plans]")
+        gen_gemm_plans(*sys.argv[2:3])
+        sys.exit(0)
     sel = sys.argv[1:] or [g for g in GROUPS if g != "ddim_full"]          # (ddim_full: 20 minutes; ask for it by name)
     for g in sel:
         print(f"[{g}]")
