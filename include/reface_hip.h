@@ -521,6 +521,25 @@ int rf_align_quad_u8(const void* frames_u8, int B, int H, int W, int Cf, int64_t
 int rf_resample_u8(const void* x_u8, int B, int H, int W, int C, const int* xbounds, const int* xk, int xksize, const int* ybounds, const int* yk,
                    int yksize, void* tmp_u8, void* out_u8, int h, int w, void* stream);
 /*
+ * crop_image's enable_padding branch (alignmengt.py:129-140; reface_amd/csrc/align_pad.hip): the crop window of every frame reflect-padded
+ * (np.pad), blurred towards the border (scipy.ndimage.gaussian_filter, fp64 accumulation, fp32 between the passes), filled towards the exact
+ * channel medians (np.median) and quantised (rint, half to even) -- byte for byte what numpy / scipy give.
+ *   rf_align_pad_u8 : frames u8 [B, H, W, Cf] as for rf_align_quad_u8 -> out u8 [B, hmax, wmax, 3]: frame b's padded image of w x h pixels in
+ *                     the top-left corner of out[b] (rows of wmax pixels; the rest of out[b] is not written), which rf_align_quad_u8 then
+ *                     reads with the window (0, 0, w, h).  desc int32 [B, 16] on the device, per frame: ox oy W0 H0 (the window in the
+ *                     frame), w h (padded size, <= wmax, hmax), the blur's radius r, then offsets into itab (int32, n_itab words) of
+ *                     extrow [h + 2 r], colmap [w], extcol [w + 2 r], colneed [w] and into dtab (fp64, n_dtab doubles) of the weights
+ *                     [r + 1] and the clip profiles c1x [w], c1y [h], c2x [w], c2y [h] -- reface_amd.align.pad_tables makes all of them.
+ *                     A descriptor that points outside the frame, the tables or its slot makes its frame a no-op; table entries are
+ *                     clamped to the image they index.  scratch_f32: 2 * B * hmax * wmax * 3 floats; select_u32: B * 1548 words.
+ *                     stages: a mask of 1 (vertical blur), 2 (horizontal blur + first mix), 4 (median select), 8 (second mix + quantise);
+ *                     15 is the whole sequence, 12 launches for any B; a subset runs those kernels on what an earlier call left in the
+ *                     scratch (tools/align_rate.py times them one by one).
+ */
+int rf_align_pad_u8(const void* frames_u8, int B, int H, int W, int Cf, int64_t frame_stride, const int* desc, const int* itab, int n_itab,
+                    const double* dtab, int n_dtab, int hmax, int wmax, float* scratch_f32, int64_t scratch_floats, void* select_u32,
+                    int64_t select_words, void* out_u8, int stages, void* stream);
+/*
  * The video dataset's per-frame preparation (ldm/data/video_swap_dataset.py:135-240) in one launch and one pass over the crops:
  *   rf_video_prep_u8 : crops u8 [B, Hc, Wc, 3] (C must be 3), labels u8 [B, h, w], lut256 u8 [256] (non-zero = a label that is cut out) and the
  *                      two tap tables of rf_resample_u8 (x: Wc -> w, y: Hc -> h; reface_amd.align.resample_taps, "bicubic" for PIL's default

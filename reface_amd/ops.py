@@ -1081,6 +1081,32 @@ def align_quad_u8(frames_u8, coeffs, out, windows=None, name="align_quad_u8"):
                   (frames_u8, coeffs, windows, out), name)
 
 
+PAD_DESC_WORDS = 16          # int32 words per frame of align_pad_u8's descriptor table
+PAD_SELECT_WORDS = 6 * 256 + 12          # uint32 words per frame of its median select
+PAD_STAGES = {"vblur": 1, "hblur_mix": 2, "median": 4, "fill": 8}
+
+
+def align_pad_u8(frames_u8, desc, itab, dtab, scratch, select, out, stages=15, name="align_pad_u8"):
+    """crop_image's enable_padding branch of frames uint8 [B, H, W, 3 | 4] (any frame stride; R, G, B are read) -> out uint8
+    [B, hmax, wmax, 3]: frame b's padded w x h image in the top-left corner of out[b], byte for byte numpy / scipy's (rf_align_pad_u8); the rest
+    of out is not written.  desc int32 [B, 16], itab int32 [n], dtab fp64 [m]: reface_amd.align.pad_tables of the batch's windows, pads and
+    blurs, on the device.  scratch fp32 [>= 2 * B * hmax * wmax * 3], select int32 [>= B * PAD_SELECT_WORDS].  stages: a sum of PAD_STAGES."""
+    lib = _lib.load()
+    _require_gpu(frames_u8, desc, itab, dtab, scratch, select, out)
+    B, H, W_, Cf = frames_u8.shape
+    hmax, wmax = out.shape[1], out.shape[2]
+    assert frames_u8.dtype == torch.uint8 and frames_u8.stride(3) == 1 and frames_u8.stride(2) == Cf and frames_u8.stride(1) == W_ * Cf
+    assert desc.dtype == torch.int32 and desc.is_contiguous() and desc.shape == (B, PAD_DESC_WORDS)
+    assert itab.dtype == torch.int32 and itab.is_contiguous() and itab.ndim == 1 and dtab.dtype == torch.float64 and dtab.is_contiguous() and dtab.ndim == 1
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.shape == (B, hmax, wmax, 3)
+    assert scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.numel() >= 2 * B * hmax * wmax * 3
+    assert select.dtype == torch.int32 and select.is_contiguous() and select.numel() >= B * PAD_SELECT_WORDS
+    assert 0 < int(stages) < 16
+    return Launch(lib.rf_align_pad_u8, (_p(frames_u8), B, H, W_, Cf, frames_u8.stride(0) if B > 1 else H * W_ * Cf, _p(desc), _p(itab), itab.numel(),
+                                        _p(dtab), dtab.numel(), hmax, wmax, _p(scratch), scratch.numel(), _p(select), select.numel(), _p(out), int(stages)),
+                  (frames_u8, desc, itab, dtab, scratch, select, out), name)
+
+
 def resample_u8(x_u8, xtaps, ytaps, tmp, out, name="resample_u8"):
     """PIL's two-pass integer resampler (Image.resize with a convolution filter) of x uint8 [B, H, W, 3 | 4] -> out uint8 [B, h, w, C] through
     tmp uint8 [B, H, w, C], byte for byte (rf_resample_u8).  xtaps / ytaps = (bounds int32 [n_out, 2], taps int32 [n_out, ksize]) on the

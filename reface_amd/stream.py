@@ -110,7 +110,7 @@ class VideoStream:
     ``state`` holds the batch's frames on the device, their indices and inverse transforms, and the crops / label maps (for --stream_keep)."""
 
     def __init__(self, landmarks, remove_labels, *, seg_ckpt=None, seg12=True, parser=None, image_size=512, crop_size=CROP_SIZE, channels=4,
-                 device="cuda", paste_mask=None):
+                 device="cuda", paste_mask=None, pad_edges=False):
         lm = np.asarray(landmarks, dtype=np.float64)
         self.src_of = fill_missing(lm)
         self.quads = {i: quad_from_landmarks(lm[i])[3] for i in sorted(set(self.src_of))}
@@ -120,13 +120,14 @@ class VideoStream:
         self.device, self.seg_ckpt, self.parser = torch.device(device), seg_ckpt, parser
         self.lut_host = keep_lut(remove_labels)
         self.paste_mask = paste_mask
+        self.pad_edges, self.padded = bool(pad_edges), []          # crop_image's padding of faces at the frame's edge; the frames it padded so far
         self.aligner = self.lut = self.taps = None
         self.last = None          # (frame index, crop u8 [1, S, S, 3], labels u8 [1, S/2, S/2]) of the last frame that had a face
 
     def _setup(self):
         if self.aligner is None:
             from .parsing import FaceParser
-            self.aligner = Aligner(self.S, device=self.device)
+            self.aligner = Aligner(self.S, device=self.device, pad_edges=True) if self.pad_edges else Aligner(self.S, device=self.device)
             self.parser = self.parser or FaceParser(self.seg_ckpt, device=self.device)
             self.lut = torch.from_numpy(self.lut_host).to(self.device)
             self.taps = tuple(torch.from_numpy(a).to(self.device) for a in resample_taps(self.S, self.size, "bicubic"))
@@ -172,6 +173,7 @@ class VideoStream:
             pool_l.append(self.last[2])
         if faces:
             crops, _ = self.aligner.align([fdev[j] for j in faces], quads=np.stack([self.quads[idx[j]] for j in faces]))
+            self.padded += [idx[faces[k]] for k in self.aligner.padded]
             labels = self.parser.parse(crops, seg12=self.seg12)
             for k, j in enumerate(faces):
                 where[idx[j]] = len(pool_c) + k

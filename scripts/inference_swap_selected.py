@@ -89,6 +89,9 @@ def build_parser():
     p.add_argument("--landmarks", type=str, default=None, help="--align: .npy of the target images' landmarks [N, 68, 2] (sorted file order; "
                    "non-finite row = no face); without it they come from dlib")
     p.add_argument("--src_landmarks", type=str, default=None, help="--align: the same for the images of --src_folder")
+    p.add_argument("--align_padding", action="store_true", help="--align: crop_image's enable_padding: a face whose crop reaches over its image's "
+                   "edge is reflect-padded, blurred towards the border and filled towards the median on the GPU (the FFHQ recipe) instead of "
+                   "showing a black wedge; other crops keep their bytes.  Its effect on swap quality is unmeasured")
     return p
 
 
@@ -137,7 +140,10 @@ def save_gpu_png(enc, device, x_img, target, kw, ref512, ids, dirs):
 
 def main(argv=None):
     opt = build_parser().parse_args(argv)
-    print(opt)
+    print(argparse.Namespace(**{k: v for k, v in vars(opt).items() if k != "align_padding" or v}))
+    if opt.align_padding and not opt.align:
+        raise SystemExit("inference_swap_selected: --align_padding pads the crops that --align makes at the image's edge; without it no image is "
+                         "aligned (the crops of target_cropped / source_cropped are read as they are)")
     align_jobs = check_align_inputs(opt) if opt.align else []
     torch.manual_seed(opt.seed)
     np.random.seed(opt.seed)
@@ -145,8 +151,11 @@ def main(argv=None):
     for files, lm, out in align_jobs:          # stage 1's alignment on the GPU
         from reface_amd.align import align_to_disk
         os.makedirs(out, exist_ok=True)
-        align_to_disk(files, lm, [os.path.join(out, f"{i}.png") for i in range(len(files))], batch=max(1, opt.n_samples))
-        print(f"inference_swap_selected: {len(files)} aligned crops written to {out}")
+        padded = []
+        align_to_disk(files, lm, [os.path.join(out, f"{i}.png") for i in range(len(files))], batch=max(1, opt.n_samples),
+                      **(dict(pad_edges=True, padded=padded) if opt.align_padding else {}))
+        print(f"inference_swap_selected: {len(files)} aligned crops written to {out}"
+              + (f" ({len(padded)} of them padded at the image's edge: --align_padding)" if opt.align_padding else ""))
     base = opt.Base_dir
     tc, tm, sc, sm = (os.path.join(base, d) for d in ("target_cropped", "mask_frames", "source_cropped", "source_mask"))
     if opt.parse_masks:             # stage 1's parsing half on the GPU: label maps of the crops whose map folder is missing or empty

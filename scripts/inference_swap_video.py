@@ -135,6 +135,10 @@ def build_parser():
     p.add_argument("--landmarks", type=str, default=None, help="--align: .npy of the frames' landmarks [N, 68, 2] (non-finite row = no face); "
                    "without it they come from dlib")
     p.add_argument("--src_landmarks", type=str, default=None, help="--align: .npy of --src_image's landmarks [68, 2]; without it they come from dlib")
+    p.add_argument("--align_padding", action="store_true", help="--align / --stream: crop_image's enable_padding for --src_image and the frames: "
+                   "a face whose crop reaches over the frame's edge is reflect-padded, blurred towards the border and filled towards the median "
+                   "on the GPU (the FFHQ recipe) instead of showing a black wedge; other crops keep their bytes.  Its effect on swap "
+                   "quality is unmeasured")
     p.add_argument("--stream", action="store_true", help="raw frames to pasted frames as one device-resident chain: the work of --align --parse_masks "
                    "--paste_back with one PNG decode and one encode per frame and no intermediate files (reads what they read; writes results/, "
                    "<video>_inv_transforms.npy and temp_results/)")
@@ -277,13 +281,23 @@ def run_align(opt, paths, lm, src_lm):
     pp = prepared_paths(opt)
     os.makedirs(pp["frames"], exist_ok=True)
     os.makedirs(os.path.dirname(pp["src"]), exist_ok=True)
-    align_to_disk([opt.src_image], src_lm, [pp["src"]])
+    padded, src_padded = [], []
+    pad = dict(pad_edges=True) if opt.align_padding else {}
+    align_to_disk([opt.src_image], src_lm, [pp["src"]], **pad, **(dict(padded=src_padded) if pad else {}))
     if opt.video_in:          # the frames as device tensors, decoded when the aligner asks for them
         paths = video_source(opt, torch.device("cuda"))
-    inv = align_to_disk(paths, lm, [os.path.join(pp["frames"], f"{i}.png") for i in range(len(paths))], batch=max(1, opt.n_samples))
+    inv = align_to_disk(paths, lm, [os.path.join(pp["frames"], f"{i}.png") for i in range(len(paths))], batch=max(1, opt.n_samples), **pad,
+                        **(dict(padded=padded) if pad else {}))
     np.save(pasteback_paths(opt)["inv_transforms"], inv)
     print(f"inference_swap_video: {len(paths)} frames aligned into {pp['frames']} ({int((~np.isfinite(lm).all(axis=(1, 2))).sum())} without a face "
-          f"repeat the previous one); inverse transforms in {pasteback_paths(opt)['inv_transforms']}")
+          f"repeat the previous one); inverse transforms in {pasteback_paths(opt)['inv_transforms']}" + padding_clause(opt, len(padded), len(src_padded)))
+
+
+def padding_clause(opt, n_frames, n_src):
+    """--align_padding: how many crops went through crop_image's padding (nothing without the flag)."""
+    if not opt.align_padding:
+        return ""
+    return f"; --align_padding padded the crops of {n_frames} frames at the frame's edge" + (" and the source crop" if n_src else "")
 
 
 def load_model_and_sampler(opt, config):
@@ -320,7 +334,8 @@ def run_stream(opt):
     config = rcfg.load(opt.config)
     test_args = dict(config.data.params.test.params)
     remove = test_args["remove_mask_tar_FFHQ"] if test_args["gray_outer_mask"] else [2, 3, 5, 6, 7]
-    vs = VideoStream(lm, remove, seg_ckpt=opt.faceParsing_ckpt, seg12=opt.seg12, paste_mask=make_paste_mask(opt, test_args))          # host fp64 only: quads and inverse transforms of EVERY frame
+    vs = VideoStream(lm, remove, seg_ckpt=opt.faceParsing_ckpt, seg12=opt.seg12, paste_mask=make_paste_mask(opt, test_args),
+                     **(dict(pad_edges=True) if opt.align_padding else {}))          # host fp64 only: quads and inverse transforms of EVERY frame
     pp, sp = prepared_paths(opt), pasteback_paths(opt)
     np.save(sp["inv_transforms"], vs.inv_transforms)
     torch.manual_seed(opt.seed)
@@ -330,7 +345,8 @@ def run_stream(opt):
     from reface_amd.align import align_to_disk
     from reface_amd.parsing import FaceParser, parse_label_maps
     os.makedirs(os.path.dirname(pp["src"]), exist_ok=True)
-    align_to_disk([opt.src_image], src_lm, [pp["src"]])
+    src_padded = []
+    align_to_disk([opt.src_image], src_lm, [pp["src"]], **(dict(pad_edges=True, padded=src_padded) if opt.align_padding else {}))
     vs.parser = FaceParser(opt.faceParsing_ckpt)
     parse_label_maps([(pp["src"], pp["src_mask"])], opt.faceParsing_ckpt, seg12=opt.seg12, parser=vs.parser)
     model, sampler, device = load_model_and_sampler(opt, config)
@@ -401,7 +417,7 @@ def run_stream(opt):
           f"transforms of all {len(paths)} frames to {sp['inv_transforms']}; "
           + (f"crops, label maps and swapped crops of the swapped frames kept in {', '.join(keep.values())}" if keep else
              "no crops, label maps or model_outputs files were written (--stream_keep writes them)")
-          + mask_clause(opt) + (video_clause(opt, video_files) if video is not None else " (the mp4 + audio mux of the reference's stage 3 is not built)."))
+          + padding_clause(opt, len(vs.padded), len(src_padded)) + mask_clause(opt) + (video_clause(opt, video_files) if video is not None else " (the mp4 + audio mux of the reference's stage 3 is not built)."))
     return n_done
 
 
@@ -470,7 +486,10 @@ def hand_over(writer, held, jobs):
 
 def main(argv=None):
     opt = build_parser().parse_args(argv)
-    print(argparse.Namespace(**{k: v for k, v in vars(opt).items() if k not in VIDEO_OPTIONS}))          # (the closing line states the video's settings)
+    print(argparse.Namespace(**{k: v for k, v in vars(opt).items() if k not in VIDEO_OPTIONS and (k != "align_padding" or v)}))          # (the closing line states the video's settings)
+    if opt.align_padding and not (opt.align or opt.stream or opt.stream_keep):
+        raise SystemExit("inference_swap_video: --align_padding pads the crops that --align or --stream make at the frame's edge; without either no "
+                         "frame is aligned (the crops of target_frames/ are read as they are)")
     if opt.gpu_png and not (opt.paste_back or opt.stream or opt.stream_keep):
         raise SystemExit("inference_swap_video: --gpu_png encodes the pasted frames of results/ and needs --paste_back or --stream "
                          "(model_outputs/ stays on the host writer)")

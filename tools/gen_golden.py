@@ -8,7 +8,7 @@ as small ``.npz`` fixtures under tests/golden/.  Only DATA is stored (tensors + 
 needed to regenerate the weights); no reference source is copied.
 
 Usage:  python tools/gen_golden.py [group ...]     (groups: schedule unet_ops unet_small unet_full
-                                                    ddim vae arcface clip e2e bisenet align idscore pose expr fid lpips)
+                                                    ddim vae arcface clip e2e bisenet align align_pad idscore pose expr fid lpips)
 
 One group records this project's own library instead of the reference and is run by name only:
         REFACE_HIP_LIB=<libreface_hip.so of the commit to record> python tools/gen_golden.py gemm_plans <commit>
@@ -645,6 +645,56 @@ def gen_align():
             out[f"{name}_crop{S}"] = np.asarray(crop)
             out[f"{name}_inv{S}"] = A.calc_alignment_coefficients(quad + 0.5, [[0, 0], [0, S], [S, S], [S, 0]])
     save("align", **out)
+
+
+# (name, H, W, frame seed, quad centre, half-axis, rotation in degrees, output size): faces over the left edge and over a corner, pads
+# larger than the window (numpy's reflect folds more than once), a window one pixel wide, a LANCZOS shrink before the pad, and a face
+# inside its frame (the padding does not trigger: today's crop)
+ALIGN_PAD_CASES = [("left_edge", 96, 128, 301, (10.3, 50.2), 22.0, 7.0, 32), ("corner", 80, 90, 302, (84.0, 75.5), 18.5, -12.0, 24),
+                   ("multi_reflect", 40, 200, 303, (100.2, 20.1), 45.0, 3.0, 32), ("one_px", 64, 64, 304, (-13.5, 30.0), 11.0, 0.0, 16),
+                   ("shrunk", 300, 400, 305, (30.0, 150.0), 70.0, 10.0, 16), ("interior", 128, 128, 306, (64.0, 64.0), 20.0, 5.0, 32)]
+
+
+def pad_case_quad(centre, half, deg):
+    a = np.radians(deg)
+    c, x = np.asarray(centre, dtype=np.float64), half * np.array([np.cos(a), np.sin(a)])
+    y = np.array([-x[1], x[0]])
+    return np.stack([c - x - y, c - x + y, c + x + y, c + x - y])
+
+
+def gen_align_pad():
+    """crop_image(..., enable_padding=True) of the reference on ALIGN_PAD_CASES: per case the frame's seed and size, the quad, S, the crop and
+    the padded u8 image the transform read (caught at PIL.Image.fromarray, which only the padding branch calls; empty when it did not run)."""
+    import importlib
+    import PIL.Image
+    for name in ("skimage", "skimage.io", "cv2", "tqdm"):
+        try:
+            importlib.import_module(name)
+        except ImportError:
+            m = ref_shims._mod(name)
+            if name == "tqdm":
+                m.tqdm = lambda it, **k: it
+    if not hasattr(PIL.Image, "ANTIALIAS"):
+        PIL.Image.ANTIALIAS = PIL.Image.LANCZOS
+    from src.utils import alignmengt as A
+    out = {"names": np.array([c[0] for c in ALIGN_PAD_CASES]), "frames": np.array([(c[1], c[2], c[3], c[7]) for c in ALIGN_PAD_CASES], dtype=np.int64)}
+    fromarray, seen = PIL.Image.fromarray, []
+
+    def spy(a, *args, **kw):
+        seen.append(np.array(a))
+        return fromarray(a, *args, **kw)
+    for name, H, W, seed, centre, half, deg, S in ALIGN_PAD_CASES:
+        quad = pad_case_quad(centre, half, deg)
+        frame = fromarray(seeded_frame(H, W, 3, seed))
+        del seen[:]
+        PIL.Image.fromarray = spy
+        try:
+            crop = A.crop_image(frame, S, quad.copy(), enable_padding=True).convert("RGB")
+        finally:
+            PIL.Image.fromarray = fromarray
+        assert crop.size == (S, S) and len(seen) == (name != "interior"), (name, len(seen))
+        out.update({f"{name}_quad": quad, f"{name}_crop": np.asarray(crop), f"{name}_padded": seen[0] if seen else np.zeros((0, 0, 3), np.uint8)})
+    save("align_pad", **out)
 
 
 def _install_tv_transforms():
@@ -1364,7 +1414,7 @@ def gen_gemm_plans(recorded_from="unknown"):
 
 GROUPS = dict(ddim_full=gen_ddim_full, unet_keys=gen_unet_keys, plms=gen_plms, schedule=gen_schedule, unet_ops=gen_unet_ops, unet_small=gen_unet_small, unet_full=gen_unet_full,
               ddim=gen_ddim, vae=gen_vae, arcface=gen_arcface, clip=gen_clip, e2e=gen_e2e,
-              bisenet=gen_bisenet, align=gen_align, idscore=gen_idscore, pose=gen_pose, expr=gen_expr, fid=gen_fid, lpips=gen_lpips)
+              bisenet=gen_bisenet, align=gen_align, align_pad=gen_align_pad, idscore=gen_idscore, pose=gen_pose, expr=gen_expr, fid=gen_fid, lpips=gen_lpips)
 
 if __name__ == "__main__":
     if sys.argv[1:2] == ["gemm_plans"]:          # (by name only, with the commit whose library is loaded: see the module's help text)
