@@ -25,7 +25,11 @@ moves an output far beyond the tolerance) but not zero (a wrong denominator show
 |v| of the tolerance's second term is >= 1 in every element, which is what lets it cover the dead keys' mass (at most 96 keys at 2^-30 and a few
 dozen at 2^-32, times 7: below 2^-20) and fp16's absolute spacing below 2^-14 where live terms cancel.
 Head-dim slots a family does not use hold noise on ONE side (odd slots in K, even slots in Q) and zero on the other: the scores do not change,
-a kernel that pairs the wrong k-steps does."""
+a kernel that pairs the wrong k-steps does.
+
+A case that carries `only` = "tail", "tiny" or "vsub" (tests/f16_range_cases.py) runs that range family in every head instead of the rotation; its weights
+lie in the band the families above exclude, so its tests call reference(check=False) and assert the family's own conditions.  No case of the table
+below names one."""
 import math
 
 import torch
@@ -109,7 +113,39 @@ def operands(c, gs, device="cpu"):
     for f, sg in ((3, 1), (4, -1)):
         q = torch.where(fam == f, torch.where(s0, a, qn), q)
         k = torch.where(fam == f, torch.where(s0, sg * lev, kn), k)
-    return q.to(F64), k.to(F64), v.to(F64)
+    only = c.get("only")          # the range families (tests/f16_range_cases.py): a case that names one runs it in every head; no rotation
+    if only == "tail":
+        # one key jmax(g) at the row maximum (score 0, inside the key range: tail keys before and after it), every other key at score -(e + f (i % 2)),
+        # e in [9, 22], f = j % 3: weights 2^-9 .. 2^-24, seven keys in eight at e >= 15 (fp16 subnormals as a packed P), in every key tile.  V: +-(200 .. 255)
+        # with ONE sign per (column, head) on the tail keys -- they add up, nothing cancels --, -1 / 0 / 1 on the maximum's key
+        h = _hash(g * 8191 + j)
+        e = torch.where((h % 8 == 0) & (j != Nk - 1), 9 + (h >> 3) % 6, 15 + (h >> 3) % 8)          # (the last key: a last tile of one key has its subnormal too)
+        jmax = Nk // 3 + (5 * g) % max(1, Nk // 3)
+        top = j == jmax
+        s1 = (t == 1)
+        q = torch.where(s0, 1, torch.where(s1, i % 2, qn)) + 0 * g
+        k = torch.where(top, 0 * kn, torch.where(s0, -e, torch.where(s1, -(j % 3), kn)))
+        v = torch.where(top, _tri((g * 37 + 11) * 173 + t), (1 - 2 * ((t + g) % 2)) * (200 + _hash((g * 4099 + j) * 211 + t) % 56))
+    q, k, v = q.to(F64), k.to(F64), v.to(F64)
+    if only == "tiny":
+        # Q is an fp16 subnormal +-m 2^-24 (m in 1 .. 3, the sign alternates per query) against K = 1 or 2 in slot 0, noise against zeros elsewhere: every
+        # score is a multiple of 2^-24 below 2^-21, the row maximum lies in (0, 2^-14) on the even queries and in (-2^-14, 0) on the odd ones.  Every
+        # weight is within 2^-21 of 1: the 16-bit pack of P rounds it to 1, 2^-21 A from the fp64 weights -- inside the unchanged limit_of.
+        # What this family pins is that subnormal Q operands and reference points below 2^-14 (the two low branches of ceil16<f16_t>, used by the dma
+        # kernels alone) are REACHED and give finite, correct output.  It cannot tell a wrong low branch from the right one: any reference point
+        # within 2^-14 of the true one gives the same weights to 2^-14, far inside limit_of
+        q = torch.where(s0, (1 - 2 * (i % 2)) * (1 + (i // 2 + g) % 3) * 2.0 ** -24, qn.to(F64))
+        k = torch.where(s0, (1 + _hash(g * 8191 + j) % 2).to(F64), kn.to(F64))
+    if only == "vsub":
+        # V in S-in against live weights: the selector family's scores (the keys of the query's target class at weight 1, every other key at <= 2^-32)
+        # with a V that depends on the key's CLASS alone: +-m 2^-24, m in 1 .. 255, an fp16 subnormal (2^-14 m, a normal value, in every fourth
+        # column).  The output is the class's own V row: the mean of n equal rows, n v / n, 2^-22 relative from v after the fp32 reciprocal and the
+        # dead keys' mass -- and v is ON the 16-bit grid, so the store rounds back to v itself: compared bit for bit
+        assert b >= 1
+        q, k = torch.where(t < b, 16 * code(qcls), qn).to(F64) + 0.0 * g, torch.where(t < b, code(kcls), kn).to(F64)
+        hv = _hash((g * 4099 + kcls) * 211 + t)
+        v = ((1 - 2 * ((hv >> 9) % 2)) * (1 + hv % 255)).to(F64) * torch.where(t % 4 == 3, 2.0 ** -14, 2.0 ** -24)
+    return q, k, v
 
 
 def representable(x):

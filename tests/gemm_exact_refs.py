@@ -31,7 +31,12 @@ INEXACT_ACTS = (ops.ACT_SILU, ops.ACT_QUICK_GELU, ops.ACT_GELU, ops.ACT_SIGMOID)
 
 _DEFAULTS = dict(op="bf16", out="f32", B=1, H=1, W=1, C0=64, C1=0, N=64, ks=1, kh=None, kw=None, creal=0, stride=1, pad=(0, 0, 0, 0), ups=0, korder=0, Cx=0, bias=True,
                  rowvec=False, res=False, act=ops.ACT_NONE, alpha=1.0, ws=0, gn=False, ln=None, wps=False, batch=1, col0=16, ldo_extra=16,
-                 sparse="W", gate_const=False, expect={}, small=None)
+                 sparse="W", gate_const=False, expect={}, small=None,
+                 # the range knobs (tests/f16_range_cases.py).  a_exp / w_exp / e_exp: power-of-two scales 2^exp of the activation, weight and epilogue-term
+                 # (bias, rowvec, residual) sides, entering unit_of; a_hi / w_hi: the largest integer of the activation / weight side; range16: the
+                 # expected 16-bit output is the store rounding of the exactly known fp32 value instead of a representable |out| <= 255.  At these
+                 # defaults nothing of a case changes
+                 a_exp=0, w_exp=0, e_exp=0, a_hi=3, w_hi=3, range16=False)
 
 
 def case(id, cells, expect, **kw):
@@ -131,16 +136,17 @@ def make_inputs(c, seed=0):
     sixteen = c["out"] == "16"
     sparse = c["sparse"] if sixteen else None
     # (fp8 forms: the power-of-two scales of {1, 2} double an operand's extreme; fp8 activations are +-1 so that a 3x3 window still fits)
-    a_hi = 1 if c["op"] == "a8" else 3
-    pmax = a_hi * (2 if c["op"] == "a8" else 1) * 3 * (2 if c["op"] in ("w8", "a8") else 1)
+    a_hi = 1 if c["op"] == "a8" else c["a_hi"]
+    w_hi = c["w_hi"]
+    pmax = min(a_hi, 3) * (2 if c["op"] == "a8" else 1) * 3 * (2 if c["op"] in ("w8", "a8") else 1)
     nnz = (NNZ_STAT if (c["ln"] == "prod" or c["gn"]) else NNZ) * 9 // pmax
     i = dict()
     if c["op"] == "x3":
         i["x0"] = _x3_values(g, lead + (H, W_, C0), 16)
     else:
         i["x0"] = _ints(g, lead + (H, W_, C0), -a_hi, a_hi)
-    i["x1"] = _ints(g, lead + (H, W_, C1), -3, 3) if C1 else None
-    i["xt"] = _ints(g, lead + (G["Ho"], G["Wo"], Cx), -3, 3) if Cx else None
+    i["x1"] = _ints(g, lead + (H, W_, C1), -c["a_hi"], c["a_hi"]) if C1 else None
+    i["xt"] = _ints(g, lead + (G["Ho"], G["Wo"], Cx), -c["a_hi"], c["a_hi"]) if Cx else None
     S = (B if c["wps"] else 1) * nb
     if c["ups"] == 2:
         # natural 3x3 weights in +-{1}: every phase sum (1, 2 or 4 taps) stays a small integer, exact in 16 bits
@@ -150,7 +156,7 @@ def make_inputs(c, seed=0):
         i["w3"] = w3
         i["w"] = None
     else:
-        w = _x3_values(g, (S, N, G["K"]), 1) if c["op"] == "x3" else _ints(g, (S, N, G["K"]), -3, 3)
+        w = _x3_values(g, (S, N, G["K"]), 1) if c["op"] == "x3" else _ints(g, (S, N, G["K"]), -w_hi, w_hi)
         if sparse == "W":
             w = _keep(g, w, nnz - 1, cover=True)
         if c["creal"]:
@@ -194,6 +200,13 @@ def make_inputs(c, seed=0):
     i["rowvec"] = _ints(g, (B, N), -7, 7) if c["rowvec"] else None
     i["res"] = _ints(g, (nb, G["M"], G["nout"]), -15, 15) if c["res"] else None
     i["slopes"] = torch.tensor([0.25, 0.5, 2.0, 1.0], dtype=F64)[torch.randint(0, 4, (N,), generator=g)] if c["act"] == ops.ACT_PRELU else None
+    if c["a_exp"] or c["w_exp"] or c["e_exp"]:
+        # the range knobs: every side times its power of two (exact in fp64; prepare() asserts that the 16-bit operands hold the result)
+        assert c["op"] in ("bf16", "f16") and not c["gate_const"] and c["ln"] is None, c["id"]
+        for keys, e in ((("x0", "x1", "xt"), c["a_exp"]), (("w", "w3"), c["w_exp"]), (("bias", "rowvec", "res"), c["e_exp"])):
+            for k in keys:
+                if i.get(k) is not None:
+                    i[k] = i[k] * 2.0 ** e
     return i
 
 
@@ -529,7 +542,9 @@ def unit_of(c, i):
     u = 1.0
     if c["act"] == ops.ACT_PRELU:
         u *= 0.25
-    return u * min(1.0, c["alpha"])
+    u *= min(1.0, c["alpha"])
+    # (the range knobs: products are multiples of 2^(a_exp + w_exp) units, epilogue terms of 2^e_exp; 1.0 = min(1.0, 1.0) at the defaults)
+    return min(u * 2.0 ** (c["a_exp"] + c["w_exp"]), u * 2.0 ** c["e_exp"])
 
 
 def magnitude_bound(c, i):
@@ -568,6 +583,22 @@ def assert_exact(c, i, ref):
     if not is_exact(c):
         return                                                 # tolerance-checked epilogue: only the pre-activation is exact
     assert torch.equal(ref, ref.float().to(F64)), c["id"]
+    if c["range16"]:
+        # the range switch: the expected 16-bit output is Tensor.to(dtype) of the exactly known fp32 value (asserted above), whatever its size.  Every
+        # epilogue term is a multiple of the unit (a steered bias included), and a statistics case stores only subnormal-band values: multiples of
+        # 2^-24 whose squares, in units of 2^-48, sum below 2^24 per statistics tile
+        u = unit_of(c, i)
+        for t in (i["bias"], i["rowvec"], i["res"]):
+            assert t is None or torch.equal((t / u).round() * u, t), c["id"]
+        if c["gn"]:
+            st_rows = 32 if c["ws"] else c["expect"]["bm"]
+            st = ref[0].float().to(out_dtype(c)).to(F64)
+            assert out_dtype(c) == torch.float16 and st.abs().max().item() < 2.0 ** -14 and st_rows <= 256, (
+                f"{c['id']}: a range16 statistics case must store fp16 values below 2^-14 only (multiples of 2^-24: the unit the exactness of the "
+                f"fp32 column sums is argued in); largest stored |value| {st.abs().max().item()}, {st_rows} rows per statistics tile")
+            sq = (st * st).reshape(-1, st_rows, st.shape[-1]).sum(1).max().item()
+            assert sq * 2.0 ** 48 < EXACT_LIMIT, (c["id"], sq)
+        return
     if c["out"] == "16":
         dt = out_dtype(c)
         if c["gn"]:
@@ -689,6 +720,7 @@ def prepare(c, i, dev):
     if c["res"]:          # the residual is a column slice too: 16 more columns per row behind it
         res = torch.zeros((nb, M, nout + 16), dtype=odt, device=dev)
         res[..., :nout] = i["res"].to(odt).to(dev)
+        assert not c["range16"] or torch.equal(res[..., :nout].cpu().to(F64), i["res"]), f"{c['id']}: a residual value is not representable in {odt}"
         res = res[..., :nout]
     ldo = c["col0"] + nout + c["ldo_extra"]
     out = guarded_rows(M, nout, ldo, c["col0"], odt, dev, nb)
